@@ -4,18 +4,28 @@ on the BASELINE.json headline config C2 -- batch 64 per GPU, synthetic
 256x192x3 images, 1 person box per image, 17 COCO keypoints, heatmap head +
 soft-argmax decode -- through the native HIP path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline needs: set-up, W untimed forwards, K
+timed steps, and one JSON line from rank 0 with the whole-job rate (`value`)
+and `ms_per_step`.  --dump-outputs DIR also writes what the last timed step
+returned as DIR/<name>.npy (same arguments -> same seeded inputs, so two
+builds can be compared output for output).
 
 One process per GPU; images shard across ranks (weak scaling, B per rank) and
 each step all-gathers the per-image keypoints/visibilities to every rank over
 RCCL (result collation), pipelined one step deep: step k's all_gather runs
 under step k + 1's forward, the last one completes inside the timed region.
-With N > 1 the labelled `configs.C4` (the C3 pipeline per rank) and
-`configs.C5` objects do the same for the full pipeline.  Rank 0 prints one JSON line with the
-whole-job rate, the dominant kernel's roofline fraction (HIP events on the
-launch stream, inside the timed region) and the CPU-oracle baseline timed on
-this host (N=1 only).
+
+--full adds everything else to the same line: the dominant kernel's roofline
+fraction (one stage-breakdown forward before the timed region, HIP events on
+the launch stream around that kernel inside it), the alternative stream count,
+the second precision, the exact-fp32 cross-check, the CPU-oracle baseline and
+parity timed on this host (N=1 only), the collation position check, and the
+labelled config objects (`configs.C1` / `C3` / `C5` at N=1; at N > 1
+`configs.C4`, the C3 pipeline per rank, and `configs.C5` with their own
+collation).
 """
 from __future__ import annotations
 
@@ -121,6 +131,14 @@ def parse(argv=None):
     ap.add_argument("--height", type=int, default=256)
     ap.add_argument("--width", type=int, default=192)
     ap.add_argument("--persons", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: stage breakdown and roofline (HIP events around the dominant kernel "
+                         "inside the timed region), alt-streams, secondary precision, exact-fp32 cross-check, CPU "
+                         "baseline and parity, collation check, config objects; the options below that tune these "
+                         "legs act only with --full (--only runs its one object either way)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (rank 0's) as DIR/<name>.npy "
+                         "in float32; past 64 MB in all, a fixed seeded sample of the larger arrays")
     ap.add_argument("--precision", default="split", choices=["fp32", "split", "mixed"],
                     help="split = fp32-accurate (the reference's precision); mixed = bf16 heatmap convs")
     ap.add_argument("--secondary", default="mixed", help="second, labelled precision line at N=1 ('' = none)")
@@ -260,6 +278,36 @@ def run_steps(steps, warmup, step_fn, dist, sync=_cuda_sync, finish=None):
         return el, out
 
 
+DUMP_BUDGET = 60 * 1000 * 1000     # bytes of array data --dump-outputs writes in all (< 64 MB with the headers)
+
+
+def dump_outputs(outdir, out):
+    """--dump-outputs: every tensor of a step's output dict (a list of
+    same-shape tensors stacked) as outdir/<name>.npy, float32 (float64 stays).
+    If they exceed DUMP_BUDGET in all, every array above an equal share of it
+    is cut to a fixed sample: its flat elements at sorted indices drawn with
+    seed 0, the same for the same shape in every run and build."""
+    import numpy as np
+    arrs = {}
+    for k, v in out.items():
+        if isinstance(v, (list, tuple)) and v and all(isinstance(t, torch.Tensor) for t in v) \
+                and len({tuple(t.shape) for t in v}) == 1:
+            v = torch.stack(list(v))
+        if isinstance(v, torch.Tensor):
+            t = v.detach().cpu()
+            arrs[k] = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+    if sum(x.nbytes for x in arrs.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(arrs)
+        for k, x in arrs.items():
+            if x.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).integers(0, x.size, share // x.itemsize))
+                arrs[k] = x.reshape(-1)[idx]
+    os.makedirs(outdir, exist_ok=True)
+    for k, x in arrs.items():
+        np.save(os.path.join(outdir, k + ".npy"), x)
+    return {k: list(x.shape) for k, x in arrs.items()}
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -360,16 +408,18 @@ def main_standin(a, world, rank, dist):
             pend.start(out)
         return out
 
-    el, _ = run_steps(a.steps, a.warmup, step, dist, sync=lambda: None, finish=pend.finish)
+    el, out = run_steps(a.steps, a.warmup, step, dist, sync=lambda: None, finish=pend.finish)
     per_rank = gather_elapsed(el, world, dist, torch.device("cpu"))
     el = max(per_rank)
     line = {"metric": "cpu-standin (launcher test; not a measurement)", "value": round(B * world * a.steps / el, 2),
             "unit": "images/s", "n_gpus": world, "world": world, "backend": "gloo" if dist else None,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 4),
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 4), "full": a.full,
             "rank_ms_per_step": [round(t / a.steps * 1e3, 4) for t in per_rank],
             "rccl_ranks": rank_census(dist, torch.device("cpu")),
             "collated": {k: list(v.shape) for k, v in coll.items()}}
-    if gather:   # every rank's slab landed at its shard's offset
+    if a.dump_outputs and rank == 0:
+        line["dumped"] = dump_outputs(a.dump_outputs, out)
+    if gather and a.full:   # every rank's slab landed at its shard's offset
         from dll.distributed import shard_range
         line["collated_ok"] = collation_check(model(batch), coll, ("keypoints", "visibilities"), P, world, rank,
                                               dist, torch.device("cpu"))
@@ -377,7 +427,7 @@ def main_standin(a, world, rank, dist):
             torch.equal(coll["visibilities"][s:e, :, 0, :, 2], torch.ones(e - s, P, 17))
             for s, e in (shard_range(B * world, world, r) for r in range(world))))
     cfgs = {}
-    for name in config_names(a, world, standin=True):
+    for name in (config_names(a, world, standin=True) if a.full or a.only else []):
         cfgs[name] = run_pipeline(name, a, torch.device("cpu"), None, world, rank, dist, cpu=False, standin=True)
     if cfgs:
         line["configs"] = cfgs
@@ -832,7 +882,7 @@ def main(argv=None):
 
     pmc = None
     pj = Path(a.pmc_json)
-    if pj.exists():
+    if (a.full or a.only) and pj.exists():
         try:
             pmc = json.loads(pj.read_text())
         except ValueError:
@@ -872,19 +922,23 @@ def main(argv=None):
 
     n_sub = max(1, min(a.streams, 4, B // 16))
     Bl = B // n_sub if B % n_sub == 0 else B / n_sub      # images per kernel launch (one sub-batch)
-    # warm-up, then one forward with every stage's events (the breakdown), then
-    # the timed region with events around the dominant MFMA kernel only (no
-    # bubbles elsewhere): its mean launch time is the roofline's denominator
+    # warm-up, then the timed region.  --full: between them one forward with
+    # every stage's events (the breakdown), and the timed region carries events
+    # around the dominant MFMA kernel only (no bubbles elsewhere): its mean
+    # launch time is the roofline's denominator
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
         pend.finish()
-    breakdown = stage_pass(m, plan, batch, 1)
     mfma_stages = ("fpn0", "hm_conv1", "hm_conv2", "hm_conv3")
-    dom = max((k for k in breakdown if k in mfma_stages), key=lambda k: breakdown[k][0], default=None)
-    plan.timing(True, stage=dom)
+    breakdown, dom = {}, None
+    if a.full:
+        breakdown = stage_pass(m, plan, batch, 1)
+        dom = max((k for k in breakdown if k in mfma_stages), key=lambda k: breakdown[k][0], default=None)
+        plan.timing(True, stage=dom)
     el, out = run_steps(a.steps, 0, step, dist, finish=pend.finish)
-    plan.timing(False)
+    if a.full:
+        plan.timing(False)
     dms, dn = plan.timing_query(dom) if dom else (0.0, 0)
     stages = {k: v[0] for k, v in breakdown.items()}
     if dn:
@@ -910,7 +964,7 @@ def main(argv=None):
         "value": round(total_imgs / el, 2), "unit": "images/s", "n_gpus": world, "world": world,
         "backend": "nccl (RCCL)" if dist else None, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
+        "full": a.full, "scaling": "weak", "vs_baseline": None,
         "rank_ms_per_step": [round(t / a.steps * 1e3, 4) for t in per_rank],
         "rccl_ranks": rank_census(dist, dev),
         "dtype": dtypes[a.precision][0], "dtype_detail": dtypes[a.precision][1],
@@ -924,16 +978,28 @@ def main(argv=None):
         "gflop_per_image": round(fl["total"] / 1e9, 3),
         "achieved_tflops_total": round(fl["total"] * total_imgs / el / 1e12, 2),
         "roofline": roof,
-        "stages_ms": {k: round(v, 4) for k, v in stages.items()},
-        "stages_note": f"per launch (one sub-batch of {Bl} images): one forward with every stage's HIP events "
-                       "before the timed region; the dominant stage's figure is its timed-region mean.  Not a "
-                       "partition of ms_per_step: the event-instrumented forward leaves a gap at every stage "
-                       "boundary (so the stages sum to more than a step), and ms_per_step is a wall-clock mean",
         "cpu_baseline": None,
     }
+    if a.full:
+        line["stages_ms"] = {k: round(v, 4) for k, v in stages.items()}
+        line["stages_note"] = (f"per launch (one sub-batch of {Bl} images): one forward with every stage's HIP "
+                               "events before the timed region; the dominant stage's figure is its timed-region "
+                               "mean.  Not a partition of ms_per_step: the event-instrumented forward leaves a gap "
+                               "at every stage boundary (so the stages sum to more than a step), and ms_per_step "
+                               "is a wall-clock mean")
     if gather:   # every rank's keypoint / visibility slab at its shard's offset in every rank's collated copy
         line["collated"] = {k: list(v.shape) for k, v in coll.items()}
-        line["collated_ok"] = collation_check(out, coll, ("keypoints", "visibilities"), P, world, rank, dist, dev)
+        if a.full:
+            line["collated_ok"] = collation_check(out, coll, ("keypoints", "visibilities"), P, world, rank, dist,
+                                                  dev)
+    if a.dump_outputs and rank == 0:
+        line["dumped"] = dump_outputs(a.dump_outputs, out)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            tdist.destroy_process_group()
+        return
     if world == 1 and a.alt_streams and a.alt_streams != a.streams and B // 16 >= 2:
         # the same model, batch and precision as concurrent sub-batches (kpd_plan_set_streams): the
         # sub-batches' kernels overlap, so this is a throughput figure only (no per-kernel timing)

@@ -4,7 +4,7 @@
 # "test smoke bench prof"); output under gpurun_out/$TAG (TAG default r05):
 #   test    pytest -m gpu (TESTS= overrides the selection, e.g. "-k nms"; TESTS_K= a -k expression with spaces)
 #   smoke   __graft_entry__.smoke()
-#   bench   the driver's exact command: python3 bench.py --gpus 1 --steps 20 --warmup 5
+#   bench   the full line: python3 bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   prof    rocprofv3 --kernel-trace --stats of the C2 driver command and of the
 #           C3 / C5 objects alone, then PMC passes (one counter group per run,
 #           kernel trace only beside --pmc) of each; prof_stages.py keeps each
@@ -53,7 +53,7 @@ for S in $STEPS; do
       || { echo "smoke rc=$?"; tail -20 "$OUT/smoke.log"; exit 1; }
     tail -1 "$OUT/smoke.log" ;;
   bench)
-    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS:-} > "$OUT/bench_driver_cmd.json" \
+    timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ${BENCH_ARGS:-} > "$OUT/bench_driver_cmd.json" \
       2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -20 "$OUT/bench.err"; exit 1; }
     summ "$OUT/bench_driver_cmd.json" ;;
   prof)
@@ -61,7 +61,7 @@ for S in $STEPS; do
     mkdir -p "$P"
     (
       cd /tmp && export TMPDIR=/tmp
-      C2="python3 $ROOTD/bench.py --gpus 1 --steps 20 --warmup 5"
+      C2="python3 $ROOTD/bench.py --gpus 1 --steps 20 --warmup 5 --full"
       C3="python3 $ROOTD/bench.py --only C3 --steps 20 --warmup 5 --no-cpu-baseline --alt-streams 0"
       C5="python3 $ROOTD/bench.py --only C5 --steps 20 --warmup 5 --no-cpu-baseline"
       for c in c2 c3 c5; do
@@ -107,7 +107,7 @@ PY
         case "${AB_CFG:-c2}" in
           c3) ARGS="--only C3 --steps 10 --warmup 5 --no-cpu-baseline --alt-streams 0" ;;
           c5) ARGS="--only C5 --steps 10 --warmup 5 --no-cpu-baseline" ;;
-          *) ARGS="--steps 20 --warmup 10 --no-cpu-baseline --configs none --secondary= --alt-streams 0 --no-exact-check" ;;
+          *) ARGS="--steps 20 --warmup 10 --full --no-cpu-baseline --configs none --secondary= --alt-streams 0 --no-exact-check" ;;
         esac
         if [ "$V" = "-" ]; then E=""; else E="$V"; fi
         env KPD_DIAG_LIB=1 $E timeout -k 10 300 python3 bench.py $ARGS > "$OUT/ab.json" 2> "$OUT/ab.err" \

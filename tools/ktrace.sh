@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 case $CFG in
   c3) ARGS="--only C3 --steps 10 --warmup 5 --no-cpu-baseline --alt-streams 0" ;;
   c5) ARGS="--only C5 --steps 10 --warmup 5 --no-cpu-baseline" ;;
-  *) ARGS="--steps 20 --warmup 10 --no-cpu-baseline --no-exact-check --configs none --secondary= --alt-streams 0" ;;
+  *) ARGS="--steps 20 --warmup 10 --full --no-cpu-baseline --no-exact-check --configs none --secondary= --alt-streams 0" ;;
 esac
 env ${ENVS:-} timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -o run -- \
   python3 "$R/bench.py" $ARGS > "$O/run.log" 2>&1 || { echo "ktrace rc=$?"; tail -5 "$O/run.log"; exit 1; }

@@ -5,7 +5,7 @@
 # variants ("-" = none), PMC_GROUPS=";"-separated counter groups.
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_ab; rm -rf $O; mkdir -p $O; cd /tmp && export TMPDIR=/tmp
-C2="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --configs none --secondary= --alt-streams 0"
+C2="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --configs none --secondary= --alt-streams 0"
 IFS=";" read -ra VARS <<< "${PMC_AB_ENVS:--}"
 IFS=";" read -ra PG <<< "${PMC_GROUPS:-FETCH_SIZE;WRITE_SIZE}"
 v=0
