@@ -223,6 +223,13 @@ int kpd_bench_conv16(int split, int N, int H, int W, int cin, int cout, int dbg,
 #define KPD_BUILD_DIAG 1
 int kpd_build_flags(void);
 
+/* Diagnostics (host only, no device needed): the packed position-class table
+ * of the split FPN level 0.  Class c = (y % 4) * 4 + x % 4: cls_ng[16] its
+ * lateral-1 pixel groups, cls_g[16 * 4] their ids (oy + 1) * 3 + (ox + 1),
+ * cls_woff[16] the f16-element offset of its weight block -- classes with the
+ * same lateral term share one block.  *blocks = the distinct group blocks. */
+int kpd_fpn0x_class_table(int* cls_ng, int* cls_g, int* cls_woff, int* blocks);
+
 /* ---- Stand-alone operators: the reference's submodule forwards and helper
  * functions, for callers that use them outside MultiPersonKeypointModel.forward.
  * Tensors are NCHW fp32 device memory, exactly as the reference modules take

@@ -566,9 +566,16 @@ __global__ __launch_bounds__(NT) void conv16_kernel(const Conv16Args p) {
 //       taps read after the 4x nearest upsample: (Y + oy, X + ox) with the taps
 //       that land there summed into one weight matrix -- 1, 2 or 4 groups of
 //       128 input channels depending on the position class (a, b).
-// Both parts accumulate into the same MFMA tile; the tile's 256 pixels are of
-// ONE class (consecutive lat1-grid pixels of one image), so each K-tile has
-// one B operand.  2.6x fewer MACs than the 3x3 conv over lat0, and lat0 (403
+// Both parts accumulate into the same MFMA tile, part (2) first; the tile's
+// 256 pixels are of ONE class (consecutive lat1-grid pixels of one image), so
+// each K-tile has one B operand.  Part (2) depends on (a, b) only through the
+// row type {0, mid, 3} and the column type {0, mid, 3}: the six class pairs of
+// kFpn0xPairFirst have the same pixels, masks and weights, so the second
+// member of a pair starts from a copy of the first member's part-(2)
+// accumulators (26 group-GEMMs per (image, row block) instead of 36: 184
+// K-tiles instead of 224).  Every pixel sums its lateral K-tiles in group
+// order, then its tap0 K-tiles, whatever the batch or the grid.
+// 2.6x fewer MACs than the 3x3 conv over lat0 (before the pairs), and lat0 (403
 // MB per step at C2) is never written.  Same fp32-accurate f16 hi/lo products
 // as conv16_kernel<split>; zero padding comes from the buffer range checks
 // (with an exact 4x upsample the taps outside the image are exactly the lat1
@@ -593,29 +600,55 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int Hf = p.Hf, Wf = p.Wf, rh = p.rh, rw = p.rw, RG = rh * rw;
-  // Persistent: one workgroup per CU walks rounds k = 0, 1, ... of the tile
-  // space; in round k it takes logical tile k*G + (rb + k) % G.  Within a
-  // round the tiles of one XCD are consecutive (xcd_remap) and the position
-  // class is fastest, so the 16 classes of an (image, row block) -- which read
-  // the same tap0 / lateral-1 pixels -- run together on one XCD and share its
-  // L2; the (rb + k) rotation walks every workgroup through the classes, so
-  // the per-class K-tile counts (9 / 13 / 21) balance out.  The next tile's
-  // first K-tiles are issued right after the K loop, so their LDS-DMA
-  // latency overlaps this tile's epilogue.
+  // Persistent: one workgroup per CU walks epochs k = 0, 1, ... of the slot
+  // space (kFpn0xSlots: 8 slots of 1-3 per-class tiles per (image, row
+  // block)); in epoch k it takes slot k*G + (rb + k) % G and runs the slot's
+  // tiles back to back.  Within an epoch the slots of one XCD are consecutive
+  // (xcd_remap) and the slot is fastest, so the 16 classes of an (image, row
+  // block) -- which read the same tap0 / lateral-1 pixels -- run together on
+  // one XCD and share its L2; the (rb + k) rotation walks every workgroup
+  // through the slots, so their K-tile counts (35 / 18 / 21) balance out.
+  // The two members of a class pair are adjacent tiles of one slot: the
+  // second starts from the first's lateral accumulators (accL below).  The
+  // next tile's first K-tiles are issued right after the K loop, so their
+  // LDS-DMA latency overlaps this tile's epilogue.
   const int ntiles = 16 * p.N * p.tpc, G = gridDim.x;
   const int rb = xcd_remap(blockIdx.x, G);
-  // Class-half order (p.order == 1): rounds come in pairs over the same G / 8
-  // (image, row block) pairs, the first round of a pair taking position
-  // classes 0-7, the second 8-15.  An XCD then holds 4 row blocks x 8
-  // classes per round: half the per-class weights (the 2.3 MB of 16 classes
-  // re-fetched by every XCD every round dominated the kernel's HBM reads),
-  // while the row blocks' input rows stay in its L2 for the second half.
-  // The (rb + k) rotation still walks each workgroup through the classes.
-  const int NJ = p.N * p.tpc, NJR = G >> 3;
-  auto tile_at = [&](int k) {
-    if (!p.order) return k * G + (rb + k) % G;
-    const int r = (rb + k) % G, nj = (k >> 1) * NJR + (r >> 3);
-    return nj < NJ ? nj * 16 + (k & 1) * 8 + (r & 7) : ntiles;
+  // With a grid of 8 XCDs x 32 workgroups an epoch covers G / 8 (image, row
+  // block) pairs, eight workgroups each: an XCD holds 4 row blocks at a time,
+  // whose input rows stay in its L2 for all their classes.  (The class-half
+  // order of the per-class rounds -- 8 of the 16 classes per round, to halve
+  // the weights an XCD re-fetched per round -- is subsumed: an epoch is one
+  // pass over all 26 weight blocks per 4 row blocks instead of two over 18.)
+  const int NJ = p.N * p.tpc;
+  // logical tile (nj * 16 + class) of slot position j in epoch k, ntiles = none
+  auto tile_at = [&](int k, int j) {
+    constexpr unsigned slots[18] = {kFpn0xSlots[0],   kFpn0xSlots[1],   kFpn0xSlots[2],   kFpn0xSlots[3],
+                                    kFpn0xSlots[4],   kFpn0xSlots[5],   kFpn0xSlots[6],   kFpn0xSlots[7],
+                                    kFpn0xSlots10[0], kFpn0xSlots10[1], kFpn0xSlots10[2], kFpn0xSlots10[3],
+                                    kFpn0xSlots10[4], kFpn0xSlots10[5], kFpn0xSlots10[6], kFpn0xSlots10[7],
+                                    kFpn0xSlots10[8], kFpn0xSlots10[9]};
+    const int sl = k * G + (rb + k) % G;
+    int nj = sl >> 3, s = sl & 7;
+    if (p.spn == 10) {   // small launches only (launch_fpn0x)
+      nj = sl / 10;
+      s = 8 + sl - nj * 10;
+    }
+    const int c = (int)(slots[s] >> (5 * j)) & 31;
+    return nj < NJ && c < 16 ? nj * 16 + c : ntiles;
+  };
+  // the tile after (k, j): the slot's next tile, or the next epoch's first
+  auto tile_next = [&](int& k, int& j) {
+    if (j < 2) {
+      const int L = tile_at(k, j + 1);
+      if (L < ntiles) {
+        ++j;
+        return L;
+      }
+    }
+    ++k;
+    j = 0;
+    return tile_at(k, 0);
   };
 
   const i32x4 rf = make_rsrc(p.f_split, p.f_bytes), rl = make_rsrc(p.l_split, p.l_bytes);
@@ -687,38 +720,40 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
   const int co_b = wave * (BN / 8) + lrow;                     // B rows of this lane (+ 8 i)
 
   // per-tile state
-  int cls = 0, n = 0, jt = 0, ca = 0, cb = 0, q0 = 0, NG = 1, KT = 0, ld = 0;
-  // masks packed: bits 0-8 = tap0 taps in the image, bits 9-12 = lat1 groups in the grid
-  unsigned f_off[A_LD], l_off[A_LD], mask[A_LD];
+  // K order of a tile: its NL lateral K-tiles (4 per group, in group order;
+  // none for the second member of a pair), then the KT0 tap0 K-tiles
+  int cls = 0, n = 0, jt = 0, ca = 0, cb = 0, q0 = 0, NG = 1, NL = 0, KT = 0, ld = 0;
+  // A row's state in one register: its tap0 pixel index (nn * Hf + y) * Wf + x
+  // (< 2^22, launch_fpn0x) | validity flags << 22: bits 0-3 the tap0 pixel has
+  // a row above / below and a column left / right in the image, bits 4-7 the
+  // same for the lateral-1 pixel in its grid, bit 8 the row is in the grid.
+  // The lateral-1 pixel index of row i is nn * RG + q (q = Y * rw + X), so the
+  // lateral offsets are one base + i * 8 pixels.
+  constexpr int FSH = 22;
+  unsigned f_off[A_LD], l_off = 0;
   const float inv_rw = 1.f / (float)rw;   // q / rw by a float product: exact for q < 2^16 (host check)
-  // Per-row offsets and masks of tile L (VALU only, no divides, one uniform
-  // LDS read of the class's group table).  Computed for the NEXT tile inside
-  // the K loop, where it overlaps the MFMAs, not between tiles where both
-  // waves of a SIMD would run it side by side (measured 3.6 us per tile).
-  auto rows = [&](int L, unsigned* fo, unsigned* lo, unsigned* mk) {
+  // Per-row offsets and flags of tile L (VALU only, no divides).  Computed for
+  // the NEXT tile inside the K loop, where it overlaps the MFMAs, not between
+  // tiles where both waves of a SIMD would run it side by side (measured 3.6
+  // us per tile) -- into this tile's registers, once its last K-tile is out
+  // (a second set next to accL spilled).
+  auto rows = [&](int L, unsigned* fo, unsigned& lo) {
     const int c = L & 15, nj = L >> 4, nn = nj / p.tpc, j = nj - nn * p.tpc;
-    const int a_ = c >> 2, b_ = c & 3, qb = j * BM, ng = s_ng[c];
-    const int4 gq = *reinterpret_cast<const int4*>(s_g + c * 4);
+    const int a_ = c >> 2, b_ = c & 3, qb = j * BM;
+    lo = (unsigned)((nn * RG + qb + wave * 32 + lrow) * 512);
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) {
       const int q = qb + wave * 32 + i * 8 + lrow;
       const int Y = (int)(((float)q + 0.5f) * inv_rw), X = q - Y * rw, y = 4 * Y + a_, x = 4 * X + b_;
-      fo[i] = (unsigned)(((nn * Hf + y) * Wf + x) * 64);
-      lo[i] = (unsigned)(((nn * rh + Y) * rw + X) * 512);
-      // validity of rows / columns -1, 0, +1 around (y, x) and (Y, X) as 3-bit sets
-      const unsigned ry = (y > 0 ? 1u : 0u) | 2u | (y + 1 < Hf ? 4u : 0u);
-      const unsigned cx = (x > 0 ? 1u : 0u) | 2u | (x + 1 < Wf ? 4u : 0u);
-      const unsigned ryl = (Y > 0 ? 1u : 0u) | 2u | (Y + 1 < rh ? 4u : 0u);
-      const unsigned cxl = (X > 0 ? 1u : 0u) | 2u | (X + 1 < rw ? 4u : 0u);
-      unsigned m = (ry & 1u ? cx : 0u) | (ry & 2u ? cx << 3 : 0u) | (ry & 4u ? cx << 6 : 0u);
-      const int gg[4] = {gq.x, gq.y, gq.z, gq.w};
-#pragma unroll
-      for (int g = 0; g < kFpn0xMaxGroups; ++g) {
-        const int oy1 = (gg[g] * 11) >> 5, ox1 = gg[g] - 3 * oy1;   // gg / 3, gg % 3 for gg < 9
-        if (g < ng && ((ryl >> oy1) & (cxl >> ox1) & 1u)) m |= 1u << (9 + g);
-      }
-      mk[i] = q < RG ? m : 0u;
+      const unsigned fl = (y > 0 ? 1u : 0u) | (y + 1 < Hf ? 2u : 0u) | (x > 0 ? 4u : 0u) | (x + 1 < Wf ? 8u : 0u) |
+                          (Y > 0 ? 16u : 0u) | (Y + 1 < rh ? 32u : 0u) | (X > 0 ? 64u : 0u) |
+                          (X + 1 < rw ? 128u : 0u) | (q < RG ? 256u : 0u);
+      fo[i] = (unsigned)((nn * Hf + y) * Wf + x) | fl << FSH;
     }
+  };
+  // the flags a tap at row offset dy, column offset dx needs (sh = 0: tap0 pixel, 4: lateral-1 pixel)
+  auto need = [](int dy, int dx, int sh) {
+    return ((dy < 0 ? 1u : 0u) | (dy > 0 ? 2u : 0u) | (dx < 0 ? 4u : 0u) | (dx > 0 ? 8u : 0u)) << sh | 256u;
   };
   auto setup = [&](int L) {
     cls = L & 15;
@@ -729,43 +764,50 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
     cb = cls & 3;
     q0 = jt * BM;                                  // first lat1-grid pixel of the tile
     NG = s_ng[cls];
-    KT = KT0 + 4 * NG;
+    NL = (kFpn0xSecondMask >> cls) & 1u ? 0 : 4 * NG;
+    KT = NL + KT0;
     ld = 0;
   };
-  // tap0 K-tile k (taps 2k, 2k+1) of a tile with rows fo / mk (class-independent B)
-  auto issue_tap0 = [&](int stage, int k, const unsigned* fo, const unsigned* mk) {
+  // tap0 K-tile k (taps 2k, 2k+1) of a tile with rows fo (class-independent B)
+  auto issue_tap0 = [&](int stage, int k, const unsigned* fo) {
     const unsigned so = stage * STAGE;
     const int t = 2 * k + f_tsel;
     const int dy = t / 3 - 1, dx = t % 3 - 1;
     const int delta = (dy * Wf + dx) * 64 + (int)f_byte;
+    const unsigned nd = t < 9 ? need(dy, dx, 0) : ~0u;   // tap 9: the zero half of K-tile 4
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) {
-      const unsigned voff = (t < 9 && ((mk[i] >> t) & 1u)) ? fo[i] + delta : OOB;
+      const unsigned voff = ((fo[i] >> FSH) & nd) == nd ? ((fo[i] << (32 - FSH)) >> (32 - FSH - 6)) + delta : OOB;
       glds16(rf, a_dst + so + i * 8 * ROWB, voff, 0);
     }
 #pragma unroll
     for (int i = 0; i < B_LD; ++i)
       glds16(rw0, b_dst + so + i * 8 * ROWB, (unsigned)(((co_b + i * 8) * KT0 + k) * ROWB + lchunk * 16), 0);
   };
-  auto issue = [&](int stage) {
+  // K-tile k of a tile of class c (ng groups, nl lateral K-tiles) with rows fo / lo
+  auto issue_at = [&](int stage, int k, int c, int ng, int nl, const unsigned* fo, unsigned lo) {
     const unsigned so = stage * STAGE;
-    if (ld < KT0) {
-      issue_tap0(stage, ld, f_off, mask);
+    if (k >= nl) {
+      issue_tap0(stage, k - nl, fo);
     } else {
-      const int k = ld - KT0, g = k >> 2, kc = k & 3;
-      const int gg = s_g[cls * 4 + g], oy = gg / 3 - 1, ox = gg % 3 - 1;
+      const int g = k >> 2, kc = k & 3;
+      const int gg = s_g[c * 4 + g], oy = gg / 3 - 1, ox = gg % 3 - 1;
       const int delta = (oy * rw + ox) * 512 + kc * 128 + lchunk * 16;
+      const unsigned nd = need(oy, ox, 4);
 #pragma unroll
       for (int i = 0; i < A_LD; ++i) {
-        const unsigned voff = ((mask[i] >> (9 + g)) & 1u) ? l_off[i] + delta : OOB;
+        const unsigned voff = ((fo[i] >> FSH) & nd) == nd ? lo + i * 8 * 512 + delta : OOB;
         glds16(rl, a_dst + so + i * 8 * ROWB, voff, 0);
       }
-      const int wbase = s_woff[cls] * 2;   // bytes
+      const int wbase = s_woff[c] * 2;   // bytes
 #pragma unroll
       for (int i = 0; i < B_LD; ++i)
         glds16(rwe, b_dst + so + i * 8 * ROWB,
-               (unsigned)(wbase + (((co_b + i * 8) * NG + g) * 4 + kc) * ROWB + lchunk * 16), 0);
+               (unsigned)(wbase + (((co_b + i * 8) * ng + g) * 4 + kc) * ROWB + lchunk * 16), 0);
     }
+  };
+  auto issue = [&](int stage) {
+    issue_at(stage, ld, cls, NG, NL, f_off, l_off);
     ++ld;
   };
 
@@ -818,28 +860,39 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
     barrier_lds();
   };
 
-  int L = tile_at(0);
+  int ek = 0, ej = 0;   // this tile's epoch and slot position
+  int L = tile_at(0, 0);
   if (L >= ntiles) return;
   setup(L);
-  rows(L, f_off, l_off, mask);
+  rows(L, f_off, l_off);
   float scale = s_unscale[n], nscale = scale;
-  static_assert(KT0 >= S, "the prefetched K-tiles of the next tile are tap0 K-tiles");
+  static_assert(KT0 >= S, "every tile has at least S K-tiles (the second member of a pair: KT0)");
+  // the lateral accumulators of a pair's first member, kept for the second
+  f32x4 accL[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) accL[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // Every round starts with its first S K-tiles issued: round 0 here, later
   // rounds by the previous round (two inside its K loop, one after it).
 #pragma unroll
   for (int s2 = 0; s2 < S; ++s2) issue(s2);
-  unsigned nf_off[A_LD], nl_off[A_LD], nmask[A_LD];   // the next tile's rows
   int sb = 0;                                          // ring stage of this tile's K-tile 0
   const bool late = p.stagger && __builtin_amdgcn_readfirstlane(wave) >= 4;   // wave-uniform (see the K loop)
   unsigned long long mt0 = 0;                          // KPD_STAMPS: shader clock at the K loop's start
   for (int round = 0; L < ntiles; ++round) {
-    const int Lnext = tile_at(round + 1);
+    const int Lnext = tile_next(ek, ej);
     const bool has_next = Lnext < ntiles;
+    // the next tile's class, groups and lateral K-tiles (its first K-tiles go out inside this K loop)
+    const int ncls = Lnext & 15, nNG = s_ng[ncls], nNL = (kFpn0xSecondMask >> ncls) & 1u ? 0 : 4 * nNG;
+    const bool first = (kFpn0xFirstMask >> cls) & 1u, second = (kFpn0xSecondMask >> cls) & 1u;
     stamp16(p.stamps, 0, 0, L);
+    // a pair's second member continues from the first's lateral sums (the
+    // previous tile of this workgroup: same image, same lateral-1 pixels)
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < FN; ++j) acc[i][j] = second ? accL[i][j] : f32x4{0.f, 0.f, 0.f, 0.f};
     {
       // K-tile 0 landed: younger are K-tiles 1, 2 (and in a round > 0 the
       // previous tile's stores)
@@ -856,6 +909,12 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
       for (int kt = 0; kt < KT; ++kt) {
         const int ns = rs + 1 == S ? 0 : rs + 1;
         const bool more = kt + 1 < KT;
+        if (first && kt == NL) {   // the lateral K-tiles are done: keep their sums for the second member
+#pragma unroll
+          for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) accL[i][j] = acc[i][j];
+        }
         __builtin_amdgcn_s_setprio(1);
         pass(fa1, fb0);
         __builtin_amdgcn_s_setprio(0);
@@ -868,7 +927,7 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
         auto issue_k = [&]() {
           if (DBG != 2) {
             if (kt + S < KT) issue(is);
-            else if (has_next) issue_tap0(is, kt + S - KT, nf_off, nmask);
+            else if (has_next) issue_at(is, kt + S - KT, ncls, nNG, nNL, f_off, l_off);
           }
           is = is + 1 == S ? 0 : is + 1;
         };
@@ -881,8 +940,9 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
         pass(fa0, fb1);
         __builtin_amdgcn_s_setprio(0);
         if (more && late) issue_k();
-        if (kt == 0 && has_next) {
-          rows(Lnext, nf_off, nl_off, nmask);
+        // this tile's last K-tile is out: its rows make way for the next tile's
+        if (kt == KT - S - 1 && has_next) {
+          rows(Lnext, f_off, l_off);
           nscale = s_unscale[(Lnext >> 4) / p.tpc];
         }
         if (more) rd_b(ns, 1, fb1);
@@ -908,12 +968,6 @@ __global__ __launch_bounds__(NT) void fpn0x_kernel(const Fpn0xArgs p) {
       const int last = sb + KT - 1;   // the stage of this tile's last K-tile
       sb = (sb + KT) % S;
       setup(Lnext);
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        f_off[i] = nf_off[i];
-        l_off[i] = nl_off[i];
-        mask[i] = nmask[i];
-      }
       ld = S - 1;
       if (DBG != 2) issue(last % S);   // the next tile's K-tile S-1 (0 .. S-2 went out inside the K loop)
       else ++ld;
@@ -2444,8 +2498,7 @@ hipError_t launch_fpn0x(const Fpn0xArgs& a, hipStream_t st) {
   // 32-bit buffer offsets of the output and statistics stores
   if ((long)a.N * a.Hf * a.Wf * 512 >= (1L << 31) || (long)a.N * 16 * a.tpc * 1024 >= (1L << 31))
     return hipErrorInvalidValue;
-  const long tiles = 16L * a.N * a.tpc;
-  // persistent: one workgroup per CU (the kernel walks the tiles in rounds)
+  // persistent: one workgroup per CU (the kernel walks the slots in epochs)
   static int ncu = 0;
   if (!ncu) {
     int dev = 0;
@@ -2453,6 +2506,9 @@ hipError_t launch_fpn0x(const Fpn0xArgs& a, hipStream_t st) {
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
       ncu = 256;
   }
+  // slots of 1-3 per-class tiles: 8 per (image, row block), or 10 shorter ones while those fit one epoch
+  const int spn = 10L * a.N * a.tpc <= ncu ? 10 : 8;
+  const long tiles = (long)spn * a.N * a.tpc;
   static const int grid_env = kpd_diag_env("KPD_FPN0X_GRID") ? atoi(kpd_diag_env("KPD_FPN0X_GRID")) : 0;   // A/B
   const long grid = std::min<long>(tiles, grid_env > 0 ? grid_env : ncu);
 #if KPD_DIAG
@@ -2465,13 +2521,7 @@ hipError_t launch_fpn0x(const Fpn0xArgs& a, hipStream_t st) {
   // evict the weights and input rows from L2), -1 % time
   static const int out_nt = kpd_diag_env("KPD_FPN0X_NT") ? atoi(kpd_diag_env("KPD_FPN0X_NT")) : 1;
   b.out_nt = out_nt;
-  // class-half tile order (the kernel's tile_at); KPD_FPN0X_ORDER=0: class-fastest rounds (A/B)
-  static const int order = kpd_diag_env("KPD_FPN0X_ORDER") ? atoi(kpd_diag_env("KPD_FPN0X_ORDER")) : 1;
-  // (every round must give each workgroup a tile until the last, so the
-  // (image, row block) count must fill whole pairs of rounds: NJ a multiple
-  // of grid / 8 and at least one pair)
-  const long NJ = (long)a.N * a.tpc;
-  b.order = (order && grid % 8 == 0 && NJ % (grid / 8) == 0 && NJ >= grid / 8) ? 1 : 0;
+  b.spn = spn;
 #if KPD_DIAG   // ablations (KPD_FPN0X_DBG=1: no MFMA, 2: no K-loop DMA, 4: one output piece); wrong results by design
   if (dbg == 1) hipLaunchKernelGGL(fpn0x_kernel<1>, dim3((unsigned)grid), dim3(NT), 0, st, b);
   else if (dbg == 2) hipLaunchKernelGGL(fpn0x_kernel<2>, dim3((unsigned)grid), dim3(NT), 0, st, b);

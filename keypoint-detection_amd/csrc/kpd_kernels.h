@@ -116,12 +116,39 @@ __host__ __device__ inline size_t hm_pos(size_t r, int y, int x) {
 // class (y % 4, x % 4), so every MFMA row of a tile uses the same weights.
 constexpr int kFpn0xMaxGroups = 4;
 constexpr int kFpn0xMaxImg = 512;   // images per fpn0x launch (per-image unscale table in LDS)
+// Class pairs.  The lateral-1 term of class (a, b) depends on a and b only
+// through the row type {0, mid, 3} and the column type {0, mid, 3}: for
+// a = 1, 2 (b = 1, 2) every tap row (column) reads the lateral-1 pixel's own
+// row (column).  The classes (1, b) | (2, b) and (a, 1) | (a, 2) therefore
+// have the same groups, pixels, masks and weights: six pairs whose second
+// member starts from the first member's lateral accumulators and runs only its
+// own tap0 K-tiles (the four centre classes as two pairs, not one quad).
+// kFpn0xPairFirst[c] is the first member of the pair c is the second member
+// of, or -1 (first members and the four corner classes).
+constexpr int kFpn0xPairFirst[16] = {-1, -1, 1, -1, -1, -1, -1, -1, 4, 5, 6, 7, -1, -1, 13, -1};
+constexpr unsigned kFpn0xSecondMask = 1u << 2 | 1u << 8 | 1u << 9 | 1u << 10 | 1u << 11 | 1u << 14;
+constexpr unsigned kFpn0xFirstMask = 1u << 1 | 1u << 4 | 1u << 5 | 1u << 6 | 1u << 7 | 1u << 13;
+// Tile schedule: an (image, row block) is 8 slots of 1-3 logical per-class
+// tiles (5 bits each, 31 = none) that one workgroup runs back to back, the two
+// members of a pair always adjacent.  K-tiles per slot: 35 18 21 18 35 18 21 18
+// (a centre pair 9 + 5, an edge pair 13 + 5, a corner 21), so a workgroup that
+// walks the slots cyclically balances to within one slot.
+constexpr unsigned kFpn0xSlot(int c0, int c1, int c2) { return (unsigned)(c0 | c1 << 5 | c2 << 10); }
+constexpr unsigned kFpn0xSlots[8] = {kFpn0xSlot(5, 9, 0),    kFpn0xSlot(1, 2, 31),   kFpn0xSlot(3, 31, 31),
+                                     kFpn0xSlot(4, 8, 31),   kFpn0xSlot(6, 10, 12),  kFpn0xSlot(13, 14, 31),
+                                     kFpn0xSlot(15, 31, 31), kFpn0xSlot(7, 11, 31)};
+// Launches too small to fill the device with 8 slots per (image, row block)
+// take 10 (every pair and every corner its own slot: at most 21 K-tiles).
+constexpr unsigned kFpn0xSlots10[10] = {kFpn0xSlot(5, 9, 31),   kFpn0xSlot(0, 31, 31),  kFpn0xSlot(1, 2, 31),
+                                        kFpn0xSlot(3, 31, 31),  kFpn0xSlot(4, 8, 31),   kFpn0xSlot(6, 10, 31),
+                                        kFpn0xSlot(12, 31, 31), kFpn0xSlot(13, 14, 31), kFpn0xSlot(15, 31, 31),
+                                        kFpn0xSlot(7, 11, 31)};
 struct Fpn0xArgs {
   const void* f_split;     // tap0 as f16 [N][Hf][Wf][hi16 | lo16] (scale 2^a_f)
   const void* l_split;     // lateral 1 as f16 [N][rh][rw][4 x (hi32 | lo32)] (scale 2^a_l)
   const void* w0;          // [128][5 K-tiles][hi16(t) hi16(t+1) lo16(t) lo16(t+1)] (scale 2^w_exp0)
-  const void* weff;        // per class: [128][groups][4 chunks][hi32 | lo32] (scale 2^w_expE)
-  int cls_woff[16];        // f16-element offset of each class block in weff
+  const void* weff;        // per distinct lateral term: [128][groups][4 chunks][hi32 | lo32] (scale 2^w_expE)
+  int cls_woff[16];        // f16-element offset of each class's block in weff (pair members share one)
   int cls_ng[16];          // lat1 pixel groups of the class (1, 2 or 4)
   int cls_g[16][kFpn0xMaxGroups];   // group g = (oy + 1) * 3 + (ox + 1)
   const float* bias;       // [128] (fpn conv + BN, folded)
@@ -133,7 +160,7 @@ struct Fpn0xArgs {
   int f_bytes, l_bytes, w0_bytes, weff_bytes;
   int stagger;             // launcher: waves 4-7 issue their K-loop DMA one pass later
   int out_nt;              // launcher: non-temporal output stores
-  int order;               // launcher: 1 = class-half tile order (grid % 8 == 0), 0 = class-fastest rounds
+  int spn;                 // launcher: slots per (image, row block), 8 (kFpn0xSlots) or 10 (kFpn0xSlots10)
   unsigned long long* stamps;   // diagnostic phase stamps [grid][8] (KPD_STAMPS), normally null
   // footprint stores (boxes != null): image n's output pixels are stored only
   // inside the rectangle its ROI aligns read -- the union over its fp_P

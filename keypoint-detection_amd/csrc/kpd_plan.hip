@@ -544,11 +544,51 @@ int pack_split_kh(kpd_plan* p, KhSplit& ks, int cin, int cout, int ntap, std::in
   return upload(p, bd, &ks.bd);
 }
 
+// the lateral-1 row (column) offset tap d = -1, 0, 1 of output row (column) 4Y + a reads
+static int fpn0x_off(int a, int d) { return a + d < 0 ? -1 : (a + d > 3 ? 1 : 0); }
+
+// Class tables (kpd_kernels.h): groups in order of the first tap that reads
+// them; one weight block per distinct lateral term -- the second member of a
+// pair must have its first member's groups and takes its offset.  Returns the
+// number of group blocks (26), -1 if a class has more than kFpn0xMaxGroups
+// groups or a pair's groups differ.
+int fpn0x_class_table(int cls_ng[16], int cls_g[16][kFpn0xMaxGroups], int cls_woff[16]) {
+  int woff = 0, blocks = 0;
+  for (int cls = 0; cls < 16; ++cls) {
+    const int a = cls >> 2, b = cls & 3;
+    int ng = 0;
+    for (int g = 0; g < kFpn0xMaxGroups; ++g) cls_g[cls][g] = 0;
+    for (int t = 0; t < 9; ++t) {
+      const int gg = (fpn0x_off(a, t / 3 - 1) + 1) * 3 + (fpn0x_off(b, t % 3 - 1) + 1);
+      int g = 0;
+      while (g < ng && cls_g[cls][g] != gg) ++g;
+      if (g == ng) {
+        if (ng == kFpn0xMaxGroups) return -1;
+        cls_g[cls][ng++] = gg;
+      }
+    }
+    cls_ng[cls] = ng;
+    if (const int first = kFpn0xPairFirst[cls]; first >= 0) {
+      if (first >= cls || kFpn0xPairFirst[first] >= 0 || cls_ng[first] != ng) return -1;
+      for (int g = 0; g < ng; ++g)
+        if (cls_g[first][g] != cls_g[cls][g]) return -1;
+      cls_woff[cls] = cls_woff[first];
+      continue;
+    }
+    cls_woff[cls] = woff;
+    woff += 128 * ng * 128 * 2;   // f16 elements (hi + lo)
+    blocks += ng;
+  }
+  return blocks;
+}
+
 // FPN level 0 by linearity (fpn0x_kernel): W0 = W3 . L0 (the 3x3 conv on the
 // 16-channel stem tap through the bias-free lateral 0) and, per output position
 // class (y % 4, x % 4), the 3x3 taps summed by the lateral-1 pixel they read
 // after the exact 4x nearest upsample.  Products in double; split into f16
 // hi + lo after a power-of-two scale (one per weight set).
+// One weight block per distinct lateral term: the second member of a class
+// pair (kFpn0xPairFirst) is checked bit-equal to the first and dropped.
 int pack_fpn0x(kpd_plan* p, const DevConv& dc, const DevConv& lat0) {
   if (dc.cin_p != 128 || dc.cout_p != 128 || lat0.cin_p != 16 || lat0.cout_p != 128) return KPD_OK;   // path unused
   const size_t n3 = (size_t)128 * 9 * 128;
@@ -567,31 +607,35 @@ int pack_fpn0x(kpd_plan* p, const DevConv& dc, const DevConv& lat0) {
         w0[((size_t)co * 9 + t) * 16 + c] = acc;
         m0 = std::max(m0, std::fabs(acc));
       }
-  // per class: tap groups by lateral-1 pixel offset
-  auto off = [](int a, int d) { return a + d < 0 ? -1 : (a + d > 3 ? 1 : 0); };
+  // per class: tap groups by lateral-1 pixel offset; the second member of a
+  // class pair (kFpn0xPairFirst) shares the first member's block
+  if (fpn0x_class_table(p->fpn0x.cls_ng, p->fpn0x.cls_g, p->fpn0x.cls_woff) < 0)
+    return fail(KPD_ESTATE, "fpn0x: more than 4 tap groups, or a class pair with different groups");
   std::vector<double> weff;
+  std::vector<size_t> src_of(16, 0);   // each class's block in weff (doubles)
   double mE = 0.0;
   int woff = 0;
   for (int cls = 0; cls < 16; ++cls) {
-    const int a = cls >> 2, b = cls & 3;
-    int gid[9], ng = 0;
-    for (int t = 0; t < 9; ++t) {
-      const int gg = (off(a, t / 3 - 1) + 1) * 3 + (off(b, t % 3 - 1) + 1);
-      int g = 0;
-      while (g < ng && p->fpn0x.cls_g[cls][g] != gg) ++g;
-      if (g == ng) {
-        if (ng == kFpn0xMaxGroups) return fail(KPD_ESTATE, "fpn0x: more than 4 tap groups");
-        p->fpn0x.cls_g[cls][ng++] = gg;
-      }
-      gid[t] = g;
-    }
-    p->fpn0x.cls_ng[cls] = ng;
-    p->fpn0x.cls_woff[cls] = woff;
+    const int a = cls >> 2, b = cls & 3, ng = p->fpn0x.cls_ng[cls];
     std::vector<double> blk((size_t)128 * ng * 128, 0.0);   // [co][g][k]
     for (int co = 0; co < 128; ++co)
-      for (int t = 0; t < 9; ++t)
-        for (int k = 0; k < 128; ++k) blk[((size_t)co * ng + gid[t]) * 128 + k] += W3(co, t, k);
+      for (int t = 0; t < 9; ++t) {
+        const int gg = (fpn0x_off(a, t / 3 - 1) + 1) * 3 + (fpn0x_off(b, t % 3 - 1) + 1);
+        int g = 0;
+        while (p->fpn0x.cls_g[cls][g] != gg) ++g;
+        for (int k = 0; k < 128; ++k) blk[((size_t)co * ng + g) * 128 + k] += W3(co, t, k);
+      }
+    if (const int first = kFpn0xPairFirst[cls]; first >= 0) {
+      // dropped only if bit-equal to the first member's (a changed fpn0x_off must not pass silently)
+      if (p->fpn0x.cls_ng[first] != ng ||
+          std::memcmp(blk.data(), weff.data() + src_of[first], blk.size() * sizeof(double)) != 0)
+        return fail(KPD_ESTATE, "fpn0x: the weights of a class pair differ");
+      src_of[cls] = src_of[first];
+      continue;
+    }
+    if (p->fpn0x.cls_woff[cls] != woff) return fail(KPD_ESTATE, "fpn0x: class table offsets");
     for (double v : blk) mE = std::max(mE, std::fabs(v));
+    src_of[cls] = weff.size();
     weff.insert(weff.end(), blk.begin(), blk.end());
     woff += 128 * ng * 128 * 2;   // f16 elements (hi + lo)
   }
@@ -618,9 +662,10 @@ int pack_fpn0x(kpd_plan* p, const DevConv& dc, const DevConv& lat0) {
       }
   // W_eff rows [co][g][kc][hi32 | lo32]
   std::vector<_Float16> hE((size_t)woff, (_Float16)0.f);
-  size_t src = 0;
   for (int cls = 0; cls < 16; ++cls) {
+    if (kFpn0xPairFirst[cls] >= 0) continue;   // the first member's block
     const int ng = p->fpn0x.cls_ng[cls];
+    const size_t src = src_of[cls];
     _Float16* dst = hE.data() + p->fpn0x.cls_woff[cls];
     for (int co = 0; co < 128; ++co)
       for (int g = 0; g < ng; ++g)
@@ -631,7 +676,6 @@ int pack_fpn0x(kpd_plan* p, const DevConv& dc, const DevConv& lat0) {
           dst[row + k % 32] = hi;
           dst[row + 32 + k % 32] = lo;
         }
-    src += (size_t)128 * ng * 128;
   }
   if (int rc = upload(p, h0, &p->fpn0x.w0)) return rc;
   if (int rc = upload(p, hE, &p->fpn0x.weff)) return rc;
@@ -870,6 +914,14 @@ extern "C" {
 const char* kpd_last_error(void) { return g_err.c_str(); }
 const char* kpd_version(void) { return "kpd 0.1 gfx950"; }
 int kpd_build_flags(void) { return KPD_DIAG ? KPD_BUILD_DIAG : 0; }
+
+int kpd_fpn0x_class_table(int* cls_ng, int* cls_g, int* cls_woff, int* blocks) {
+  if (!cls_ng || !cls_g || !cls_woff || !blocks) return fail(KPD_EINVAL, "NULL output");
+  const int nb = fpn0x_class_table(cls_ng, reinterpret_cast<int(*)[kFpn0xMaxGroups]>(cls_g), cls_woff);
+  if (nb < 0) return fail(KPD_ESTATE, "fpn0x: inconsistent class table");
+  *blocks = nb;
+  return KPD_OK;
+}
 
 int kpd_plan_create(int device, int in_channels, kpd_plan** out) {
   if (!out) return fail(KPD_EINVAL, "out is NULL");

@@ -28,7 +28,7 @@ PRECISIONS = {"fp32": KPD_PRECISION_FP32, "split": KPD_PRECISION_SPLIT, "mixed":
 EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_tensor",
            "kpd_plan_finalize", "kpd_plan_destroy", "kpd_forward", "kpd_debug_copy", "kpd_nms",
            "kpd_plan_timing", "kpd_plan_timing_stage", "kpd_plan_timing_query", "kpd_plan_set_detector",
-           "kpd_bench_conv16", "kpd_build_flags",
+           "kpd_bench_conv16", "kpd_build_flags", "kpd_fpn0x_class_table",
            "kpd_plan_set_streams", "kpd_preprocess", "kpd_target_heatmaps", "kpd_keypoint_metrics",
            "kpd_heatmap_head", "kpd_keypoint_head", "kpd_backbone", "kpd_channel_attention", "kpd_decode_heatmaps",
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
@@ -86,6 +86,7 @@ def load() -> ctypes.CDLL:
     lib.kpd_target_heatmaps.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
     lib.kpd_keypoint_metrics.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_float),
                                          c_int, c_void_p, c_void_p]
+    lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float
     lib.kpd_heatmap_head.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

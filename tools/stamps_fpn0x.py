@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Phase stamps of fpn0x_kernel (KPD_STAMPS): per workgroup the prologue
 (first K-tile landed), the K loop, the statistics exchange and the stores
-(drained), grouped by K-tile count (position classes with 1, 2 or 4 lateral-1
-tap groups).  GPU only:  KPD_STAMPS=1 python3 tools/stamps_fpn0x.py"""
+(drained), grouped by K-tile count (5: the second member of a class pair, which
+runs its tap0 K-tiles only; 9 / 13: first members with 1 / 2 lateral-1 tap
+groups; 21: the corner classes).  GPU only:  KPD_STAMPS=1 python3 tools/stamps_fpn0x.py"""
 import os
 import sys
 from pathlib import Path
