@@ -126,6 +126,24 @@ int kpd_plan_timing(kpd_plan* plan, int enable);
 int kpd_plan_timing_stage(kpd_plan* plan, const char* stage);
 int kpd_plan_timing_query(kpd_plan* plan, const char* stage, double* total_ms, int* count);
 
+/* Dispatch path log (diagnostics; host side only, results unchanged).  The
+ * forward picks between specialised kernels by image size and batch;
+ * kpd_plan_path_log(plan, 1) makes every later eager forward (kpd_forward,
+ * kpd_backbone, kpd_backbone_body, and the stand-alone kpd_heatmap_head /
+ * kpd_keypoint_head) record which branch each dispatch point took.
+ * kpd_plan_path_query copies the last such call's distinct tokens, one per
+ * line in order of first use, e.g.
+ *   f1:dwsum+se16_proj  f2:fir23:t8  f4:exdw+seproj:po192  lateral:chain
+ *   level0:fpn0x:tpc3  hm:hmconv:split
+ * (f<i> = features.<i>, lat<i> = FPN lateral i) into buf as a C string and
+ * writes the size it needs, terminator included, to *need (both nullable).
+ * A replayed hipGraph takes no decision and leaves the list empty.  With
+ * plan == NULL the list is every token this build can emit, "*" standing
+ * for a block / lateral index or a value chosen at run time.  Off (the
+ * default) a dispatch point costs one branch. */
+int kpd_plan_path_log(kpd_plan* plan, int enable);
+int kpd_plan_path_query(kpd_plan* plan, char* buf, size_t bytes, size_t* need);
+
 /* Greedy NMS on one set of n cxcywh boxes (device), reference semantics
  * (IoU > thr suppressed, score-descending order, ties -> lower index).
  * keep: [n] int32 out (first *n_keep valid), n_keep: [1] int32 out (device).

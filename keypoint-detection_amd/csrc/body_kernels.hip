@@ -1568,6 +1568,7 @@ hipError_t launch_exdw(const ExDwArgs& a, int N, int K, int S, hipStream_t st) {
   static const bool rtact = kpd_diag_env("KPD_EXDW_RTACT") != nullptr;
   const bool hs = !rtact && a.act_e == ACT_HSWISH && a.act_d == ACT_HSWISH;
   if (exdw_bl(a, K)) {
+    kpd_path(xt4 ? KP_EXDW_BL_XT4 : KP_EXDW_BL_XT2);
     if (hs && xt4) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 4, 6, true, ACT_HSWISH>), grid, dim3(256), lds, st, a);
     else if (hs) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 2, 6, true, ACT_HSWISH>), grid, dim3(256), lds, st, a);
     else if (xt4) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 4, 6, true>), grid, dim3(256), lds, st, a);
@@ -1577,14 +1578,17 @@ hipError_t launch_exdw(const ExDwArgs& a, int N, int K, int S, hipStream_t st) {
   // the hardswish instances the model's blocks take: features.4 (5x5 s2, 16-channel slices of 32
   // input channels), .5-.8 (5x5 s1, 16-channel slices, 48 input channels), .9 (5x5 s2, 32-channel slices)
   if (hs && K == 5 && S == 2 && a.CS == 16 && kc == 2 && xt4) {
+    kpd_path(KP_EXDW_HS_S2C16);
     hipLaunchKernelGGL((exdw_kernel<5, 2, 1, 4, 2, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
     return hipGetLastError();
   }
   if (hs && K == 5 && S == 1 && a.CS == 16 && kc == 3 && xt4) {
+    kpd_path(KP_EXDW_HS_S1C16);
     hipLaunchKernelGGL((exdw_kernel<5, 1, 1, 4, 3, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
     return hipGetLastError();
   }
   if (hs && K == 5 && S == 2 && a.CS == 32 && kc == 3 && !xt4) {
+    kpd_path(KP_EXDW_HS_S2C32);
     hipLaunchKernelGGL((exdw_kernel<5, 2, 2, 2, 3, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
     return hipGetLastError();
   }
@@ -1606,6 +1610,7 @@ hipError_t launch_exdw(const ExDwArgs& a, int N, int K, int S, hipStream_t st) {
       EXDW_KC(KK, SS, 3, 2);                            \
     }                                                   \
   } while (0)
+  kpd_path(a.CS != 48 && xt4 ? KP_EXDW_RT_XT4 : KP_EXDW_RT_XT2);
   if (K == 3 && S == 1) EXDW(3, 1);
   else if (K == 5 && S == 1) EXDW(5, 1);
   else if (K == 5 && S == 2) EXDW(5, 2);
@@ -1652,6 +1657,13 @@ hipError_t launch_seproj(const SeProjArgs& a, int N, hipStream_t st) {
     if (nwv == 8) hipLaunchKernelGGL((seproj_kernel<M, T, 8>), grid, dim3(512), lds_m, st, b);     \
     else hipLaunchKernelGGL((seproj_kernel<M, T, 4>), grid, dim3(256), lds_m, st, b);              \
   } while (0)
+  if (mt == 3 && ntt == 1) kpd_path(KP_SEPROJ_M3T1, nwv);
+  else if (mt == 3 && ntt == 2) kpd_path(KP_SEPROJ_M3T2, nwv);
+  else if (mt == 3 && ntt == 3) kpd_path(KP_SEPROJ_M3T3, nwv);
+  else if (mt == 6 && ntt == 1) kpd_path(KP_SEPROJ_M6T1, nwv);
+  else if (mt == 4 && ntt == 1) kpd_path(KP_SEPROJ_M4T1, nwv);
+  else if (mt == 12 && ntt == 1) kpd_path(KP_SEPROJ_M12T1, nwv);
+  else if (mt == 12 && ntt == 3) kpd_path(KP_SEPROJ_M12T3, nwv);
   if (mt == 3 && ntt == 1) SEP(3, 1);
   else if (mt == 3 && ntt == 2) SEP(3, 2);
   else if (mt == 3 && ntt == 3) SEP(3, 3);

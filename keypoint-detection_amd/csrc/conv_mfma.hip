@@ -330,6 +330,10 @@ hipError_t launch(const ConvArgs& a0, hipStream_t st) {
   if (a.k_split > 1) chunk_l = std::min<long>(chunk_l, a.splitk_cap / (HW * a.cout_p * a.k_split));
   if (chunk_l < 1) a.k_split = 1, chunk_l = std::min<long>(a.N, kMaxDesc / img_bytes);
   const int chunk = (int)chunk_l;
+  if (sizeof(TA) != 4) kpd_path(KP_CONV_BF16);
+  else if (KS == 3) kpd_path(KP_CONV_K3);
+  else if (BM == 64) kpd_path(a.k_split > 1 ? KP_CONV_K1_BM64_SPLITK : KP_CONV_K1_BM64);
+  else kpd_path(a.k_split > 1 ? KP_CONV_K1_BM128_SPLITK : KP_CONV_K1_BM128);
   for (int n0 = 0; n0 < a0.N; n0 += chunk) {
     const int nb = std::min(chunk, a0.N - n0);
     a.N = nb;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 struct ConvArgs {
   const void* in;        // NHWC [N][H][W][in_cstride] (TA)
@@ -385,6 +386,111 @@ hipError_t launch_kh_final(const float* lin_r, int r_stride, const float* lin_v,
 // error reporting shared with the C ABI entry points outside kpd_plan.hip
 int kpd_fail_einval(const char* msg);
 int kpd_fail_hip(hipError_t e, const char* where);
+
+// ---- dispatch path log (kpd_plan_path_log / kpd_plan_path_query; host only) ----
+// Which branch each dispatch point of a forward took.  One row per branch:
+// X(id, name, sites).  A token reads <site>:<name>; the site is where the
+// forward stands when the branch is taken (f<i> = body block features.<i>,
+// lat<i> = FPN lateral i), "%d" in a name is a value chosen at run time (a
+// row tile, fpn0x tiles per class).  sites = the sites a row can be emitted
+// at; KP_DIAG rows need a switch of the diagnostic build.  The listing
+// (kpd_plan_path_query(NULL)) prints "*" for a block / lateral index or a value.
+enum : unsigned {
+  KP_TOP = 1, KP_BLOCK = 2, KP_LAST = 4, KP_LAT = 8, KP_FPN0 = 16, KP_PD = 32, KP_HM = 64, KP_KH = 128, KP_DIAG = 256
+};
+#define KPD_PATH_TOKENS(X)                                                                         \
+  /* forward_one: MobileNet body blocks */                                                         \
+  X(KP_F1_DWSUM, "dwsum+se16_proj", KP_BLOCK)                                                      \
+  X(KP_FIR23, "fir23:t%d", KP_BLOCK)                                                               \
+  X(KP_FIR, "fir:th%d", KP_BLOCK)                                                                  \
+  X(KP_EXDW_SEPROJ48, "exdw+seproj:po48", KP_BLOCK)                                                \
+  X(KP_EXDW_SEPROJ192, "exdw+seproj:po192", KP_BLOCK)                                              \
+  X(KP_EXDW_SE, "exdw+se_kernel+project", KP_BLOCK)                                                \
+  X(KP_EXDW_PLAIN, "exdw+project", KP_BLOCK)                                                       \
+  X(KP_GENERIC_SE, "generic+se_kernel", KP_BLOCK)                                                  \
+  X(KP_GENERIC, "generic", KP_BLOCK)                                                               \
+  X(KP_SE_EXCITE, "se_excite", KP_BLOCK)                                                           \
+  /* launch_exdw */                                                                                \
+  X(KP_EXDW_BL_XT4, "exdw:bl:xt4", KP_BLOCK)                                                       \
+  X(KP_EXDW_BL_XT2, "exdw:bl:xt2", KP_BLOCK)                                                       \
+  X(KP_EXDW_HS_S2C16, "exdw:hs:k5s2:cs16:xt4", KP_BLOCK)                                           \
+  X(KP_EXDW_HS_S1C16, "exdw:hs:k5s1:cs16:xt4", KP_BLOCK)                                           \
+  X(KP_EXDW_HS_S2C32, "exdw:hs:k5s2:cs32:xt2", KP_BLOCK)                                           \
+  X(KP_EXDW_RT_XT4, "exdw:rt:xt4", KP_BLOCK)                                                       \
+  X(KP_EXDW_RT_XT2, "exdw:rt:xt2", KP_BLOCK)                                                       \
+  /* launch_seproj: row tiles per workgroup, 16-column tiles, waves */                             \
+  X(KP_SEPROJ_M3T1, "seproj:m3:t1:w%d", KP_BLOCK)                                                  \
+  X(KP_SEPROJ_M3T2, "seproj:m3:t2:w%d", KP_BLOCK)                                                  \
+  X(KP_SEPROJ_M3T3, "seproj:m3:t3:w%d", KP_BLOCK)                                                  \
+  X(KP_SEPROJ_M6T1, "seproj:m6:t1:w%d", KP_BLOCK | KP_DIAG)                                        \
+  X(KP_SEPROJ_M4T1, "seproj:m4:t1:w%d", KP_BLOCK | KP_DIAG)                                        \
+  X(KP_SEPROJ_M12T1, "seproj:m12:t1:w%d", KP_BLOCK | KP_DIAG)                                      \
+  X(KP_SEPROJ_M12T3, "seproj:m12:t3:w%d", KP_BLOCK | KP_DIAG)                                      \
+  /* conv() / launch_conv / launch_pw_small */                                                     \
+  X(KP_CONV_PW_SMALL, "conv:pw_small", KP_BLOCK | KP_LAST | KP_LAT)                                \
+  X(KP_CONV_K3, "conv:k3", KP_FPN0 | KP_HM | KP_KH)                                                \
+  X(KP_CONV_K1_BM64, "conv:k1:bm64", KP_BLOCK | KP_LAST | KP_LAT | KP_PD | KP_KH)                  \
+  X(KP_CONV_K1_BM128, "conv:k1:bm128", KP_BLOCK | KP_LAST | KP_LAT | KP_PD | KP_KH)                \
+  X(KP_CONV_K1_BM64_SPLITK, "conv:k1:bm64+splitk", KP_BLOCK | KP_LAT | KP_KH)                      \
+  X(KP_CONV_K1_BM128_SPLITK, "conv:k1:bm128+splitk", KP_BLOCK)                                     \
+  X(KP_CONV_BF16, "conv:bf16", KP_HM | KP_DIAG)                                                    \
+  /* FPN laterals */                                                                               \
+  X(KP_LAT_CHAIN, "lateral:chain", KP_TOP)                                                         \
+  X(KP_LAT_PER_LEVEL, "lateral:per_level", KP_TOP)                                                 \
+  X(KP_LC_SPLIT_SMALL_REUSE, "lateral_chain:split:small+reuse", KP_TOP)                            \
+  X(KP_LC_SPLIT_BIG_REUSE, "lateral_chain:split:big+reuse", KP_TOP)                                \
+  X(KP_LC_SPLIT_SMALL, "lateral_chain:split:small", KP_TOP | KP_DIAG)                              \
+  X(KP_LC_SPLIT_BIG, "lateral_chain:split:big", KP_TOP)                                            \
+  X(KP_LC_F32_SMALL, "lateral_chain:fp32:small", KP_TOP)                                           \
+  X(KP_LC_F32_BIG, "lateral_chain:fp32:big", KP_TOP)                                               \
+  X(KP_SPLIT_ROWS, "split_rows", KP_LAT)                                                           \
+  X(KP_LATERAL_STREAM, "lateral_stream", KP_LAT)                                                   \
+  /* FPN level 0, channel statistics, top-k */                                                     \
+  X(KP_L0_FPN0X, "level0:fpn0x:tpc%d", KP_TOP)                                                     \
+  X(KP_L0_CONV_STATS, "level0:conv+stats", KP_TOP)                                                 \
+  X(KP_L0_CONV, "level0:conv", KP_TOP)                                                             \
+  X(KP_CHANNEL_STATS, "topk:channel_stats", KP_TOP)                                                \
+  X(KP_TOPK_SLOTMAP, "topk+slotmap", KP_TOP)                                                       \
+  X(KP_SLOTMAP, "slotmap", KP_TOP)                                                                 \
+  /* person detector, ROI stage */                                                                 \
+  X(KP_PD_FUSED, "detector:fused", KP_TOP)                                                         \
+  X(KP_PD_UNFUSED, "detector:unfused", KP_TOP)                                                     \
+  X(KP_ROI_KH, "roi:roi_kh", KP_TOP)                                                               \
+  X(KP_ROI_ALIGN, "roi:roi_align", KP_TOP)                                                         \
+  X(KP_ROI_ALIGN128, "roi:roi_align128", KP_TOP)                                                   \
+  /* run_heatmap_head */                                                                           \
+  X(KP_HM_ATTN, "attn", KP_HM)                                                                     \
+  X(KP_HM_ATTN_2K, "spool+sapply", KP_HM | KP_DIAG)                                                \
+  X(KP_HM_HMCONV_SPLIT, "hmconv:split", KP_HM)                                                     \
+  X(KP_HM_HMCONV_BF16, "hmconv:bf16", KP_HM)                                                       \
+  X(KP_HM_CONV16, "conv16", KP_HM | KP_DIAG)                                                       \
+  X(KP_HM_FINAL_FUSED, "final:fused", KP_HM)                                                       \
+  X(KP_HM_FINAL, "final:separate", KP_HM)                                                          \
+  /* run_keypoint_head */                                                                          \
+  X(KP_KH_SPLIT_XREADY, "split:x_ready", KP_KH)                                                    \
+  X(KP_KH_SPLIT_ATT1, "split:att1", KP_KH | KP_DIAG)                                               \
+  X(KP_KH_SPLIT_ATT2, "split:att2", KP_KH)                                                         \
+  X(KP_KH_FP32, "fp32", KP_KH)
+enum KpdPath : int {
+#define KPD_PATH_ID(id, name, sites) id,
+  KPD_PATH_TOKENS(KPD_PATH_ID)
+#undef KPD_PATH_ID
+  KP_COUNT
+};
+struct KpdPathEntry { unsigned site; int idx, tok, val; };
+struct KpdPathLog {
+  unsigned site = KP_TOP;   // where the forward stands (forward_one moves it)
+  int idx = -1;             // block / lateral index of the site
+  std::vector<KpdPathEntry> e;
+};
+extern thread_local KpdPathLog* g_kpd_path;   // null (the default): logging off
+void kpd_path_add(int tok, int val);
+inline void kpd_path(int tok, int val = -1) {
+  if (__builtin_expect(g_kpd_path != nullptr, 0)) kpd_path_add(tok, val);
+}
+inline void kpd_path_at(unsigned site, int idx = -1) {
+  if (__builtin_expect(g_kpd_path != nullptr, 0)) { g_kpd_path->site = site; g_kpd_path->idx = idx; }
+}
 
 // ---- stand-alone operators (ops_kernels.hip) ----
 // mode: KPD_DECODE_* (include/kpd.h)

@@ -47,6 +47,49 @@ int kpd_fail_hip(hipError_t e, const char* where) {
   return fail(KPD_EHIP, std::string(where) + ": " + hipGetErrorString(e));
 }
 
+// ------------------------------------------------------------------ dispatch path log
+thread_local KpdPathLog* g_kpd_path = nullptr;
+
+namespace {
+struct PathRow { const char* name; unsigned sites; };
+const PathRow kPathRows[KP_COUNT] = {
+#define KPD_PATH_ROW(id, name, sites) {name, sites},
+    KPD_PATH_TOKENS(KPD_PATH_ROW)
+#undef KPD_PATH_ROW
+};
+const struct { unsigned site; const char* prefix; } kPathSites[] = {
+    {KP_TOP, ""},       {KP_BLOCK, "f%d:"}, {KP_LAST, "last:"}, {KP_LAT, "lat%d:"},
+    {KP_FPN0, "fpn0:"}, {KP_PD, "pd:"},     {KP_HM, "hm:"},     {KP_KH, "kh:"}};
+
+// "%d" -> the value, or "*" in the listing (v < 0)
+std::string path_fill(const char* fmt, int v) {
+  std::string s(fmt);
+  const size_t at = s.find("%d");
+  if (at != std::string::npos) s.replace(at, 2, v < 0 ? "*" : std::to_string(v));
+  return s;
+}
+std::string path_token(unsigned site, int idx, int tok, int val) {
+  std::string s;
+  for (const auto& ps : kPathSites)
+    if (ps.site == site) s = path_fill(ps.prefix, idx);
+  return s + path_fill(kPathRows[tok].name, val);
+}
+
+// forward_one's scope: the launchers log into the plan's list while it runs
+struct PathScope {
+  explicit PathScope(kpd_plan* p);
+  ~PathScope() { g_kpd_path = nullptr; }
+};
+}  // namespace
+
+// (enabled only) one entry per distinct token, in order of first use
+void kpd_path_add(int tok, int val) {
+  KpdPathLog& l = *g_kpd_path;
+  for (const KpdPathEntry& e : l.e)
+    if (e.site == l.site && e.idx == l.idx && e.tok == tok && e.val == val) return;
+  l.e.push_back({l.site, l.idx, tok, val});
+}
+
 namespace {
 
 struct HostT {
@@ -257,12 +300,20 @@ struct kpd_plan {
   unsigned long long* stamps = nullptr;   // KPD_STAMPS diagnostic buffer (kStampWords)
   // per-stage HIP-event timing (kpd_plan_timing)
   struct Timer { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; };
+  // dispatch path log (kpd_plan_path_log): the last forward's tokens; empty and untouched while off
+  bool path_on = false;
+  KpdPathLog path;
   bool timing = false;
   std::string timing_only;   // non-empty: record only this stage (kpd_plan_timing_stage)
   std::map<std::string, Timer> timers;
 };
 
 namespace {
+
+PathScope::PathScope(kpd_plan* p) {
+  g_kpd_path = p->path_on ? &p->path : nullptr;
+  kpd_path_at(KP_TOP);
+}
 
 // ------------------------------------------------------------------ weight helpers
 const HostT* get(kpd_plan* p, const std::string& name, std::string& missing) {
@@ -843,6 +894,7 @@ int conv(const DevConv& L, const void* in, int N, int H, int W, int in_cstride, 
   a.splitk_ws = g_splitk; a.splitk_cap = kSplitKFloats;
   const ConvDType dt = !L.bf16 ? CONV_F32 : (out_kind == 1 ? CONV_BF16_OUT_BF16 : CONV_BF16_OUT_F32);
   if (L.k == 1 && !L.bf16 && out_kind == 0 && pw_small_ok(a)) {   // small-K 1x1: direct-to-fragment MFMA
+    kpd_path(KP_CONV_PW_SMALL);
     HIP_TRY(launch_pw_small(a, st));
     return KPD_OK;
   }
@@ -865,6 +917,7 @@ int hm_conv(const kpd_plan* p, const DevConv& L, const void* in, int R, int in_c
             const HmSplit* sp = nullptr) {
   if (L.ws) {   // fp32-accurate split products on the padded ROI maps
     if (!sp || !hm_padded(p)) return fail(KPD_EINVAL, "split heatmap conv needs the padded layout and bounds");
+    kpd_path(KP_HM_HMCONV_SPLIT);
     HmConvArgs h{};
     h.in = in; h.wt = L.ws; h.bias = L.b; h.out = out; h.R = R; h.cin = L.cin_p; h.cout = L.cout_p;
     h.stamps = stamps;
@@ -882,6 +935,7 @@ int hm_conv(const kpd_plan* p, const DevConv& L, const void* in, int R, int in_c
   if (!L.bf16) return conv(L, in, R, 56, 56, in_cstride, out, ACT_RELU, nullptr, 0, 0, nullptr, nullptr, 0, 0, st);
   if (hm_padded(p)) {
     if (in_cstride != L.cin_p) return fail(KPD_EINVAL, "hmconv: input channel stride must equal cin");
+    kpd_path(KP_HM_HMCONV_BF16);
     HmConvArgs h{};
     h.in = in; h.wt = L.w; h.bias = L.b; h.out = out; h.R = R; h.cin = L.cin_p; h.cout = L.cout_p;
     h.stamps = stamps;
@@ -894,6 +948,7 @@ int hm_conv(const kpd_plan* p, const DevConv& L, const void* in, int R, int in_c
     HIP_TRY(launch_hmconv(h, st));
     return KPD_OK;
   }
+  kpd_path(KP_HM_CONV16);
   Conv16Args a{};
   if (fin) {
     if (out_kind != 2 || L.cout_p != 64) return fail(KPD_EINVAL, "fused final layer needs the 64-channel conv");
@@ -1285,6 +1340,7 @@ static int run_heatmap_head(kpd_plan* p, Work& w, int R, int P, float* heat_out,
   const bool bf = p->precision == KPD_PRECISION_MIXED;
   const int xs_mode = hsplit ? 3 : bf ? (hm_padded(p) ? 2 : 1) : 0;
   static const bool att_2k = kpd_diag_env("KPD_HM_ATT_2K") != nullptr;   // A/B: pool and apply as two launches
+  kpd_path(att_2k ? KP_HM_ATTN_2K : KP_HM_ATTN);
   if (att_2k) {
     HIP_TRY(launch_hm_spool(w.roi, w.cw, R, w.smap, st));
     HIP_TRY(launch_hm_sapply(w.roi, w.cw, w.smap, p->sa_w, p->sa_b, R, w.xs, xs_mode, st, w.hsc,
@@ -1315,6 +1371,7 @@ static int run_heatmap_head(kpd_plan* p, Work& w, int R, int P, float* heat_out,
   if (int rc = hm_conv(p, p->hm3, w.h2, R, p->hm2.cout_p, w.h3, 2, st, fin_fused ? &fin : nullptr, stamps3, &sp3))
     return rc;
   c3.reset();
+  kpd_path(fin_fused ? KP_HM_FINAL_FUSED : KP_HM_FINAL);
   if (!fin_fused) HIP_TRY(launch_hm_final(w.h3, R, p->fin_w, p->fin_b, w.slot, P, heat_out, st));
   return KPD_OK;
 }
@@ -1337,12 +1394,14 @@ static int run_keypoint_head(kpd_plan* p, Work& w, int R, int P, float* kh_kpts,
     // conv's operand (KPD_KH_ATT1=1: the fp32 1x1 conv + apply kernel, A/B).
     static const bool att1 = kpd_diag_env("KPD_KH_ATT1") != nullptr;
     if (x_ready) {
-      // (roi_kh_kernel)
+      kpd_path(KP_KH_SPLIT_XREADY);   // (roi_kh_kernel)
     } else if (att1 || !p->kh_sa1.ws) {
+      kpd_path(KP_KH_SPLIT_ATT1);
       if (int rc = conv(p->kh_sa1, w.kx, R, 56, 56, 128, w.ksa, ACT_RELU6, nullptr, 0, 0, nullptr, nullptr, 0, 0, st))
         return rc;
       HIP_TRY(launch_kh_att_split(w.kx, w.ksa, p->kh_sa2_w, p->kh_sa2_b, R, bound, bdiv, bstride, w.hsc, w.kxs, st));
     } else {
+      kpd_path(KP_KH_SPLIT_ATT2);
       HIP_TRY(launch_kh_att2(w.kx, p->kh_sa1.ws, p->kh_sa1.w_exp, p->kh_sa1.b, p->kh_sa2_w, p->kh_sa2_b, R, bound,
                              bdiv, bstride, w.hsc, w.kxs, st));
     }
@@ -1374,6 +1433,7 @@ static int run_keypoint_head(kpd_plan* p, Work& w, int R, int P, float* kh_kpts,
                             kh_vis, st));
     return KPD_OK;
   }
+  kpd_path(KP_KH_FP32);
   if (int rc = conv(p->kh_sa1, w.kx, R, 56, 56, 128, w.ksa, ACT_RELU6, nullptr, 0, 0, nullptr, nullptr, 0, 0, st))
     return rc;
   HIP_TRY(launch_kh_att(w.kx, w.ksa, p->kh_sa2_w, p->kh_sa2_b, px, st));
@@ -1425,6 +1485,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
                        float* box_scores, int32_t* topk_out, hipStream_t st, hipEvent_t mark_ev = nullptr,
                        int mark_at = 0) {
   const bool detect = flags & KPD_FLAG_DETECT, dual = flags & KPD_FLAG_DUAL_HEAD;
+  const PathScope path_scope(p);
   // pipelined sub-batches: mark_ev is recorded once this sub-batch has passed
   // stage mark_at (1 body, 2 FPN laterals, 3 FPN level 0, 4 top-k, 5 ROI align)
   auto mark = [&](int at) -> int {
@@ -1484,6 +1545,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     const DevBneck& bn = p->bn[i];
     const int hi = d.h[i], wi = d.w[i], ho = d.h[i + 1], wo = d.w[i + 1];
     const int inp = pad16(bn.cfg.cin);
+    kpd_path_at(KP_BLOCK, i + 1);
     // coarse maps: expand + depthwise (+ SE means) fused when the image fits LDS
     ExDwArgs xa{};
     xa.x = x; xa.Hi = hi; xa.Wi = wi; xa.cin_p = inp;
@@ -1505,6 +1567,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
         bn.project.cin_p == 16 && bn.project.k == 1 && !bn.project.bf16 && bn.se.sq <= 16 && bn.dw.k == 3 &&
         !(bn.cfg.s == 1 && bn.cfg.cin == bn.cfg.cout) && 4 * ((wo + 3) / 4) * 4 <= 256) {
       int nt = 0;
+      kpd_path(KP_F1_DWSUM);
       HIP_TRY(launch_dwsum(x, B, hi, wi, bn.dw.w, bn.dw.b, bn.dw.act, w.d[i], ho, wo, bn.dw.k, bn.dw.s, w.separt, &nt,
                            st));
       HIP_TRY(launch_se16_proj(w.d[i], B, ho * wo, nt, w.separt, bn.se.w1, bn.se.b1, bn.se.w2, bn.se.b2, bn.se.sq,
@@ -1535,6 +1598,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
       fa.out = w.o[i + 1]; fa.H2 = ho; fa.W2 = wo;
       if (f23 && d.h[i + 2] == ho && d.w[i + 2] == wo && fir23_pick_rows(fa)) {
         fa.stamps = take_stamps("stamps_fir23_0", (size_t)((ho + fa.T - 1) / fa.T) * B);
+        kpd_path(KP_FIR23, fa.T);
         HIP_TRY(launch_fir23(fa, B, st));
         ++i;   // features.3 done too
         x = w.o[i];
@@ -1554,6 +1618,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
       fa.res = bn.cfg.s == 1 && bn.cfg.cin == bn.cfg.cout;
       if (fir_pick_rows(fa, bn.dw.k, bn.dw.s)) {
         fa.stamps = take_stamps("stamps_fir_" + std::to_string(i), (size_t)((ho + fa.TH - 1) / fa.TH) * B);
+        kpd_path(KP_FIR, fa.TH);
         HIP_TRY(launch_fir(fa, B, bn.dw.k, bn.dw.s, st));
         x = w.o[i];
         if (i + 1 == 3) taps[1] = x;
@@ -1585,6 +1650,9 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     if (fused) {
       if (seproj) {
         xa.part = w.separt; xa.w1 = bn.se.w1; xa.sq = bn.se.sq; xa.C = bn.se.C;
+        kpd_path(ho * wo == 48 ? KP_EXDW_SEPROJ48 : KP_EXDW_SEPROJ192);
+      } else {
+        kpd_path(bn.cfg.se ? KP_EXDW_SE : KP_EXDW_PLAIN);
       }
       xa.stamps = take_stamps("stamps_exdw_" + std::to_string(i), (size_t)(bn.dw.Cp / xa.CS) * B * std::max(1, xa.nband));
       HIP_TRY(launch_exdw(xa, B, bn.dw.k, bn.dw.s, st));
@@ -1609,6 +1677,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
       // pass per image instead of one per project workgroup)
       static const int se_split_env = kpd_diag_env("KPD_SE_SPLIT") ? atoi(kpd_diag_env("KPD_SE_SPLIT")) : -1;   // A/B
       if (se_split_env == 1 || (se_split_env < 0 && bn.se.C >= 288)) {
+        kpd_path(KP_SE_EXCITE);
         HIP_TRY(launch_se_excite(sa, B, w.sesc[i], st));
         sa.sesc = w.sesc[i];
       }
@@ -1621,6 +1690,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     }
     if (!fused) {
       const float* e = x;
+      kpd_path(bn.cfg.se ? KP_GENERIC_SE : KP_GENERIC);
       if (bn.has_exp) {
         if (int rc = conv(bn.expand, x, B, hi, wi, inp, w.e[i], bn.cfg.act, nullptr, 0, 0, nullptr, nullptr, 0, 0, st))
           return rc;
@@ -1639,9 +1709,11 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     if (i + 1 == 3) taps[1] = x;
     if (i + 1 == 8) taps[2] = x;
   }
+  kpd_path_at(KP_LAST);
   if (int rc = conv(p->last, x, B, d.h[11], d.w[11], pad16(96), w.last, ACT_HSWISH, nullptr, 0, 0, nullptr,
                     nullptr, 0, 0, st))
     return rc;
+  kpd_path_at(KP_TOP);
   taps[3] = w.last;
   body_stage.reset();
   if (p->body_only) {   // kpd_backbone_body
@@ -1681,22 +1753,30 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
                      p->lat[1].cin_p == lc.c1 && p->lat[2].cin_p == lc.c2 && p->lat[3].cin_p == lc.c3 &&
                      p->lat[1].cout_p == 128 && p->lat[2].cout_p == 128 && p->lat[3].cout_p == 128 &&
                      lateral_chain_ok(lc);
+  kpd_path(chain ? KP_LAT_CHAIN : KP_LAT_PER_LEVEL);
   if (chain) HIP_TRY(launch_lateral_chain(lc, B, st));
   for (int i = 3; i >= 0; --i) {
     if (chain && i > 0) continue;
     const DevConv& L = p->lat[i];
+    kpd_path_at(KP_LAT, i);
     const float* res = i < 3 ? w.lat[i + 1] : nullptr;
     if (i == 0 && lin) {   // no lateral 0: tap0 and lateral 1 go to the split layouts fpn0x_kernel reads
       char* base = reinterpret_cast<char*>(w.lat[0]);
-      if (!chain || !lc.t0)
+      if (!chain || !lc.t0) {
+        kpd_path(KP_SPLIT_ROWS);
         HIP_TRY(launch_split_rows(taps[0], B, (long)lh[0] * lw[0], 16, w.sc, 0, p->fpn0x.w_exp0, p->fpn0x.w_expE,
                                   base, st));
-      if (!chain)
+      }
+      if (!chain) {
+        kpd_path_at(KP_LAT, 1);
+        kpd_path(KP_SPLIT_ROWS);
         HIP_TRY(launch_split_rows(w.lat[1], B, (long)lh[1] * lw[1], 128, w.sc, 1, p->fpn0x.w_exp0,
                                   p->fpn0x.w_expE, base + (size_t)B * lh[0] * lw[0] * 64, st));
+      }
       continue;
     }
     if (i == 0 && L.cin_p <= 32) {   // the 16-channel stem tap: a 403 MB/step stream, not a GEMM
+      kpd_path(KP_LATERAL_STREAM);
       HIP_TRY(launch_lateral_stream(taps[0], L.cin_p, (const float*)L.w, L.b, res, B, lh[0], lw[0], lh[1], lw[1],
                                     w.lat[0], st));
       continue;
@@ -1707,6 +1787,7 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
       return rc;
   }
   lat_stage.reset();
+  kpd_path_at(KP_TOP);
   if (int rc = mark(2)) return rc;
   std::unique_ptr<Stage> fpn_stage(new Stage(p, "fpn0", st));
   // caller boxes: level 0 is stored only where the ROI aligns read it (the
@@ -1733,18 +1814,27 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     if (footprint) {
       a.fp_boxes = boxes; a.fp_NB = NB; a.fp_P = P;
     }
+    kpd_path(KP_L0_FPN0X, tpc);
     HIP_TRY(launch_fpn0x(a, st));
-  } else if (int rc = conv(p->fpn0, w.lat[0], B, d.Hf, d.Wf, 128, w.feat, ACT_RELU, nullptr, 0, 0, nullptr,
-                           d.fused_stats ? w.stats : nullptr, d.tiles, 0, st)) {
-    return rc;
+  } else {
+    kpd_path(d.fused_stats ? KP_L0_CONV_STATS : KP_L0_CONV);
+    kpd_path_at(KP_FPN0);
+    if (int rc = conv(p->fpn0, w.lat[0], B, d.Hf, d.Wf, 128, w.feat, ACT_RELU, nullptr, 0, 0, nullptr,
+                      d.fused_stats ? w.stats : nullptr, d.tiles, 0, st))
+      return rc;
+    kpd_path_at(KP_TOP);
   }
   fpn_stage.reset();
   if (int rc = mark(3)) return rc;
   std::unique_ptr<Stage> topk_stage(new Stage(p, "topk", st));
   if (!p->has_ca) return KPD_OK;   // backbone-only plan (kpd_backbone)
-  if (!d.fused_stats) HIP_TRY(launch_channel_stats(w.feat, B, HWf, 128, d.tiles, w.stats, st));
+  if (!d.fused_stats) {
+    kpd_path(KP_CHANNEL_STATS);
+    HIP_TRY(launch_channel_stats(w.feat, B, HWf, 128, d.tiles, w.stats, st));
+  }
   // given boxes for every image: the slot map rides along with the top-k launch
   const bool slot_in_topk = !detect && NB == B && NB * P > 0 && boxes != nullptr;
+  if (slot_in_topk) kpd_path(KP_TOPK_SLOTMAP);
   HIP_TRY(launch_topk(w.stats, B, d.tiles, HWf, p->ca_w0, p->ca_b0, p->ca_w2, p->ca_b2, w.topk, w.scores, st,
                       slot_in_topk ? boxes : nullptr, P, slot_in_topk ? w.slot : nullptr, w.imax,
                       lin ? w.sc : nullptr, B));
@@ -1768,13 +1858,17 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
     static const bool pd_unfused = kpd_diag_env("KPD_PD_UNFUSED") != nullptr;
     if (!pd_unfused && p->pd.cin == 128 && p->pd.cin_p == 128 && p->pd.cout_p == 48 && !p->pd.bf16 &&
         person_detect_fits(d.Wf)) {
+      kpd_path(KP_PD_FUSED);
       HIP_TRY(launch_person_detect(w.feat, B, d.Hf, d.Wf, static_cast<const float*>(p->pd.w), p->pd.b, p->anchors, H,
                                    W, p->det_conf, w.pd_boxes, w.pd_scores, st));
     } else {
+      kpd_path(KP_PD_UNFUSED);
       HIP_TRY(launch_adaptive_pool56(w.feat, B, d.Hf, d.Wf, 128, w.pd_pool, st));
+      kpd_path_at(KP_PD);
       if (int rc = conv(p->pd, w.pd_pool, B, 56, 56, 128, w.pd_head, ACT_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0,
                         st))
         return rc;
+      kpd_path_at(KP_TOP);
       HIP_TRY(launch_person_decode(w.pd_head, B, p->pd.cout_p, p->anchors, H, W, p->det_conf, w.pd_boxes,
                                    w.pd_scores, st));
     }
@@ -1797,7 +1891,11 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
                       kpd_diag_env("KPD_KH_ATT1") == nullptr;
   {
     Stage sg(p, "roi_align", st);
-    if (!slot_in_topk) HIP_TRY(launch_slotmap(boxes, NB, P, w.slot, st));
+    if (!slot_in_topk) {
+      kpd_path(KP_SLOTMAP);
+      HIP_TRY(launch_slotmap(boxes, NB, P, w.slot, st));
+    }
+    kpd_path(roi_kh ? KP_ROI_KH : KP_ROI_ALIGN);
     if (roi_kh)
       HIP_TRY(launch_roi_kh(w.feat, d.Hf, d.Wf, w.topk, boxes, R, P, w.roi, w.roi_stats, p->kh_sa1.ws,
                             p->kh_sa1.w_exp, p->kh_sa1.b, p->kh_sa2_w, p->kh_sa2_b, w.imax, P, 1, w.hsc, w.kxs, st,
@@ -1808,11 +1906,13 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
   }
   if (int rc = mark(5)) return rc;
   if (debug) p->debug["roi"] = {w.roi, sizeof(float) * (size_t)R * 3136 * 64};
+  kpd_path_at(KP_HM);
   if (int rc = run_heatmap_head(p, w, R, P, heat_out, st, KPD_HEAD_ALL, nullptr,
                                  take_stamps("stamps_hm2", (size_t)(((long)R * kHmRoiPos - kHmPitch + 255) / 224) * 2),
                                  take_stamps("stamps_hm3", (size_t)(((long)R * kHmRoiPos - kHmPitch + 255) / 256) * 2),
                                  take_stamps("stamps_hm1", (size_t)(((long)R * kHmRoiPos - kHmPitch + 255) / 224) * 2)))
     return rc;
+  kpd_path_at(KP_TOP);
   {
     Stage sg(p, "hm_final_decode", st);
     HIP_TRY(launch_decode(heat_out, boxes, w.slot, R, P, kpts, vis, st));
@@ -1820,7 +1920,11 @@ static int forward_one(kpd_plan* p, int k, bool debug, const float* image, int B
   if (dual) {
     // KEYPOINT_HEAD on ROI-align of the 128-channel FPN level 0 (keypoint_head.py:51-62)
     Stage sg(p, "keypoint_head", st);
-    if (!roi_kh) HIP_TRY(launch_roi_align(w.feat, d.Hf, d.Wf, 128, nullptr, boxes, R, P, w.kx, nullptr, st));
+    if (!roi_kh) {
+      kpd_path(KP_ROI_ALIGN128);
+      HIP_TRY(launch_roi_align(w.feat, d.Hf, d.Wf, 128, nullptr, boxes, R, P, w.kx, nullptr, st));
+    }
+    kpd_path_at(KP_KH);
     const long khrows = (long)R * kHmRoiPos - kHmPitch;
     // sized for 256-row tiles, the smallest launch_hmconv_kh picks (KPD_KH_BM256 /
     // KPD_KH_TPS1 take them for every conv; by default convs 2 / 3 use 384 / 512)
@@ -1886,6 +1990,7 @@ int kpd_forward(kpd_plan* p, const float* image, int B, int C, int H, int W, flo
         HIP_TRY(hipMemsetAsync(p->work[k].sc, 0, (size_t)2 * p->dims[k].B * kAmaxStride * sizeof(float), st));
         p->work[k].sc_dirty = false;
       }
+    if (p->path_on) p->path.e.clear();   // a replay takes no dispatch decision
     return launch_graph(g, st);
   }
   if (g.exec) {   // stale (re-carve, re-finalize, detector change): its last launch may still be running
@@ -1968,6 +2073,7 @@ static int forward_impl(kpd_plan* p, const float* image, int B, int C, int H, in
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->device));
   p->debug.clear();
+  if (p->path_on) p->path.e.clear();
 
   // Images are independent (eval BN, per-image ROI loops -- SURVEY §8(e)), so
   // a large batch runs as S contiguous sub-batches on S streams: the many
@@ -2057,6 +2163,32 @@ int kpd_plan_set_detector(kpd_plan* p, float conf_threshold, float nms_iou_thres
   return KPD_OK;
 }
 
+int kpd_plan_path_log(kpd_plan* p, int enable) {
+  if (!p) return fail(KPD_EINVAL, "null plan");
+  p->path_on = enable != 0;
+  p->path.e.clear();
+  return KPD_OK;
+}
+
+int kpd_plan_path_query(kpd_plan* p, char* buf, size_t bytes, size_t* need) {
+  std::string s;
+  if (p) {
+    for (const KpdPathEntry& e : p->path.e) s += path_token(e.site, e.idx, e.tok, e.val) + "\n";
+  } else {   // every token this build can emit: each row at each of its sites
+    for (int t = 0; t < KP_COUNT; ++t) {
+      if ((kPathRows[t].sites & KP_DIAG) && !KPD_DIAG) continue;
+      for (const auto& ps : kPathSites)
+        if (kPathRows[t].sites & ps.site) s += path_token(ps.site, -1, t, -1) + "\n";
+    }
+  }
+  if (!s.empty()) s.pop_back();
+  if (need) *need = s.size() + 1;
+  if (!buf) return KPD_OK;
+  if (bytes < s.size() + 1) return fail(KPD_EINVAL, "destination too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return KPD_OK;
+}
+
 int kpd_plan_timing(kpd_plan* p, int enable) {
   if (!p) return fail(KPD_EINVAL, "null plan");
   p->timing = enable != 0;
@@ -2129,6 +2261,9 @@ int kpd_heatmap_head(kpd_plan* p, const float* x, int R, int H, int W, int parts
   HIP_TRY(hipSetDevice(p->device));
   Work* w = nullptr;
   if (int rc = op_work(p, R, 0, st, &w)) return rc;
+  if (p->path_on) p->path.e.clear();
+  const PathScope path_scope(p);
+  kpd_path_at(KP_HM);
   // any input sign: the split convs' bound is max |x| (hsc[r][2]), not the max
   const bool hsplit = p->precision == KPD_PRECISION_SPLIT;
   if (hsplit) HIP_TRY(hipMemsetAsync(w->hsc, 0, sizeof(float) * 4 * R, st));
@@ -2149,6 +2284,9 @@ int kpd_keypoint_head(kpd_plan* p, const float* x, int R, int H, int W, float* k
   HIP_TRY(hipSetDevice(p->device));
   Work* w = nullptr;
   if (int rc = op_work(p, R, KPD_FLAG_DUAL_HEAD, st, &w)) return rc;
+  if (p->path_on) p->path.e.clear();
+  const PathScope path_scope(p);
+  kpd_path_at(KP_KH);
   // any input sign: the split path's bound is max |x| per ROI (hsc[r][2])
   if (p->kh_split) HIP_TRY(hipMemsetAsync(w->hsc, 0, sizeof(float) * 4 * R, st));
   HIP_TRY(launch_nchw_rows_to_nhwc(x, R, 128, 56, 56, w->kx, nullptr, st, p->kh_split ? w->hsc + 2 : nullptr, 4));
@@ -2169,6 +2307,7 @@ int kpd_backbone(kpd_plan* p, const float* image, int B, int C, int H, int W, fl
     if (!o) return fail(KPD_EINVAL, "null output pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->device));
+  if (p->path_on) p->path.e.clear();
   // level sizes: stem (features.0), features.3, .8, .12 -- as forward_one's Dims
   int h[12], wd[12];
   h[0] = (H - 1) / 2 + 1; wd[0] = (W - 1) / 2 + 1;
@@ -2209,6 +2348,7 @@ int kpd_backbone_body(kpd_plan* p, const float* image, int B, int C, int H, int 
     if (!o) return fail(KPD_EINVAL, "null output pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(p->device));
+  if (p->path_on) p->path.e.clear();
   int h[12], wd[12];
   h[0] = (H - 1) / 2 + 1; wd[0] = (W - 1) / 2 + 1;
   for (int i = 0; i < 11; ++i) {

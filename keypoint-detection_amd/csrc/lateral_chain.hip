@@ -349,13 +349,17 @@ hipError_t launch_lateral_chain(const LatChainArgs& a, int B, hipStream_t st) {
   static const bool noreuse = kpd_diag_env("KPD_LC_NOREUSE") != nullptr;
   const bool reuse = !noreuse && (long)a.h1 * a.w1 <= 6 * NW * 16;
   if (a.lat1_split && small && reuse) {
+    kpd_path(KP_LC_SPLIT_SMALL_REUSE);
     hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 3, 6, true, true>), grid, block, lds, st, q);
   } else if (a.lat1_split && reuse) {
+    kpd_path(KP_LC_SPLIT_BIG_REUSE);
     hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 8, 6, true, true>), grid, block, lds, st, q);
   } else if (a.lat1_split) {
+    kpd_path(small ? KP_LC_SPLIT_SMALL : KP_LC_SPLIT_BIG);
     if (small) hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 3, 6, true>), grid, block, lds, st, q);
     else hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 8, 6, true>), grid, block, lds, st, q);
   } else {
+    kpd_path(small ? KP_LC_F32_SMALL : KP_LC_F32_BIG);
     if (small) hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 3, 6, false>), grid, block, lds, st, q);
     else hipLaunchKernelGGL((lateral_chain_kernel<2, 3, 36, 8, 6, false>), grid, block, lds, st, q);
   }

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 from pathlib import Path
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -32,10 +32,12 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_plan_set_streams", "kpd_preprocess", "kpd_target_heatmaps", "kpd_keypoint_metrics",
            "kpd_heatmap_head", "kpd_keypoint_head", "kpd_backbone", "kpd_channel_attention", "kpd_decode_heatmaps",
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
-           "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn")
+           "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
+           "kpd_plan_path_log", "kpd_plan_path_query")
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
+FPN_IN_CHANNELS = (16, 24, 48, 576)   # LightweightFPN's lateral input widths (backbone.py)
 HEAD_CHANNEL_ATT, HEAD_SPATIAL_ATT, HEAD_CONVS, HEAD_ALL = 1, 2, 4, 7
 DECODE_ARGMAX, DECODE_SUBPIXEL, DECODE_SOFTARGMAX, DECODE_MODEL = 0, 1, 2, 3
 STAGES = ("body", "fpn_lateral", "fpn0", "topk", "person_detect", "roi_align", "hm_attention", "hm_conv1",
@@ -83,6 +85,8 @@ def load() -> ctypes.CDLL:
     lib.kpd_plan_timing_stage.argtypes = [c_void_p, c_char_p]
     lib.kpd_plan_timing_query.argtypes = [c_void_p, c_char_p, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(c_int)]
+    lib.kpd_plan_path_log.argtypes = [c_void_p, c_int]
+    lib.kpd_plan_path_query.argtypes = [c_void_p, c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.kpd_target_heatmaps.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
     lib.kpd_keypoint_metrics.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_float),
                                          c_int, c_void_p, c_void_p]
@@ -203,6 +207,14 @@ class Plan:
               "kpd_plan_timing_query")
         return ms.value, n.value
 
+    def path_log(self, enable: bool) -> None:
+        """Record which kernel each dispatch point of the following eager forwards takes (kpd_plan_path_log)."""
+        check(self.lib.kpd_plan_path_log(self.h, 1 if enable else 0), "kpd_plan_path_log")
+
+    def paths(self) -> List[str]:
+        """The last forward's dispatch tokens in order of first use, e.g. ``f4:exdw+seproj:po192``."""
+        return _path_query(self.lib, self.h)
+
     # ---- stand-alone operators (the reference's submodule forwards) ----
     def heatmap_head(self, x: torch.Tensor, parts: int = HEAD_ALL):
         """HeatmapHead stages on x [R,64,56,56] -> (heat [R,17,56,56] or None,
@@ -257,9 +269,18 @@ class Plan:
         """LightweightFPN.forward on four caller taps [B,c_i,h_i,w_i] -> four
         [B,128,h_i,w_i] levels (kpd_backbone_fpn)."""
         feats = [_dev_f32(f, f"features[{i}]") for i, f in enumerate(feats)]
+        if len(feats) != len(FPN_IN_CHANNELS):
+            raise ValueError(f"Expected {len(FPN_IN_CHANNELS)} features, got {len(feats)}")
         B = feats[0].shape[0]
         if any(f.dim() != 4 or f.shape[0] != B for f in feats):
             raise ValueError("FPN features must be [B, C, H, W] with one batch size")
+        # the reference's lateral nn.Conv2d rejects a tap of the wrong width; the
+        # native conv would read the tensor with its own channel count
+        for i, (f, c) in enumerate(zip(feats, FPN_IN_CHANNELS)):
+            if f.shape[1] != c:
+                raise RuntimeError(f"Given groups=1, weight of size [128, {c}, 1, 1], expected input"
+                                   f"{list(f.shape)} to have {c} channels, but got {f.shape[1]} channels instead "
+                                   f"(FPN features[{i}])")
         sizes = (ctypes.c_int * 8)(*[v for f in feats for v in f.shape[2:]])
         outs = [torch.empty(B, 128, *f.shape[2:], device=f.device) for f in feats]
         with torch.cuda.device(self.device):
@@ -287,6 +308,19 @@ class Plan:
         check(self.lib.kpd_debug_copy(self.h, name.encode(), _ptr(out), n.value, None, _stream(self.device)),
               "kpd_debug_copy")
         return out
+
+
+def _path_query(lib, handle) -> List[str]:
+    n = ctypes.c_size_t()
+    check(lib.kpd_plan_path_query(handle, None, 0, ctypes.byref(n)), "kpd_plan_path_query")
+    buf = ctypes.create_string_buffer(n.value)
+    check(lib.kpd_plan_path_query(handle, buf, n.value, None), "kpd_plan_path_query")
+    return [t for t in buf.value.decode().split("\n") if t]
+
+
+def all_paths() -> List[str]:
+    """Every dispatch token the loaded library can emit ("*" = an index or a run-time value)."""
+    return _path_query(load(), None)
 
 
 def _level_sizes(H: int, W: int):

@@ -45,6 +45,27 @@ def test_plan_argument_validation():
     lib.kpd_plan_destroy(h)
 
 
+def test_path_token_listing():
+    """kpd_plan_path_query(NULL, ...) lists every dispatch token of the build
+    without a device: distinct <site>:<name> strings, "*" for an index or a
+    run-time value, none of the diagnostic build's rows; the size protocol and
+    the argument checks of the two entry points."""
+    from dll import _native
+    lib = _native.load()
+    need = ctypes.c_size_t()
+    assert lib.kpd_plan_path_query(None, None, 0, ctypes.byref(need)) == 0 and need.value > 1
+    small = ctypes.create_string_buffer(need.value - 1)
+    assert lib.kpd_plan_path_query(None, small, need.value - 1, None) == -1
+    assert b"too small" in lib.kpd_last_error()
+    tokens = _native.all_paths()
+    assert len("\n".join(tokens)) + 1 == need.value
+    assert len(tokens) == len(set(tokens)) and all(re.fullmatch(r"[a-z0-9_+:*]+", t) for t in tokens)
+    for t in ("f*:exdw+seproj:po192", "f*:fir23:t*", "lat*:lateral_stream", "level0:fpn0x:tpc*", "hm:hmconv:split"):
+        assert t in tokens, t
+    assert "hm:conv16" not in tokens and "lateral_chain:split:small" not in tokens   # diagnostic-build rows
+    assert lib.kpd_plan_path_log(None, 1) == -1
+
+
 def test_model_rejects_cpu_input():
     from dll import _native
     from dll.configs import ModelConfig, TrainingConfig

@@ -252,8 +252,40 @@ def test_backbone_body_and_fpn_submodules(model_sd, hw):
     for i in range(4):
         np.testing.assert_allclose(got[i].cpu().numpy(), O.fpn_level(lats[i], model_sd, i).numpy(), rtol=1e-5,
                                    atol=2e-5)
+    # level 0 at 50 x 37 over level 1 at 13 x 9: neither ratio an integer
+    # (lateral_stream's nearest index floor(y * 13 / 50), floor(x * 9 / 37))
+    odd2 = [torch.rand(1, c, h, w, generator=g) for c, (h, w) in zip((16, 24, 48, 576),
+                                                                      ((50, 37), (13, 9), (6, 5), (3, 2)))]
+    got = m.backbone.fpn([o.to(DEV) for o in odd2])
+    lats = O.fpn_laterals(odd2, model_sd)
+    for i in range(4):
+        np.testing.assert_allclose(got[i].cpu().numpy(), O.fpn_level(lats[i], model_sd, i).numpy(), rtol=1e-5,
+                                   atol=2e-5)
     with pytest.raises(ValueError):
         m.backbone.fpn(list(taps.values())[:3])
+
+
+def test_fpn_rejects_wrong_channel_count(model_sd):
+    """A tap with the wrong channel count raises the reference's error (its
+    lateral nn.Conv2d's RuntimeError) before any native call: the native conv
+    would read the tensor with its own channel count.  Slot 1 (24 channels)
+    gets a 16-channel tensor, through the module and through Plan.fpn."""
+    m = _model(model_sd)
+    g = torch.Generator().manual_seed(6)
+    feats = [torch.rand(1, c, h, w, generator=g).to(DEV)
+             for c, (h, w) in zip((16, 16, 48, 576), ((32, 24), (8, 6), (4, 3), (2, 2)))]
+    with pytest.raises(RuntimeError, match="to have 24 channels, but got 16 channels"):
+        m.backbone.fpn(feats)
+    plan = m.backbone.fpn._plans.get(m.backbone.fpn, DEV, "fp32")
+    calls = []
+    real = plan.lib.kpd_backbone_fpn
+    plan.lib.kpd_backbone_fpn = lambda *a: calls.append(a) or 0
+    try:
+        with pytest.raises(RuntimeError, match="channels"):
+            plan.fpn(feats)
+    finally:
+        plan.lib.kpd_backbone_fpn = real
+    assert calls == [], "the channel check must come before the native call"
 
 
 def test_person_head_forward(model_sd):
