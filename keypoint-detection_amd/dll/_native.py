@@ -415,8 +415,10 @@ def conv3x3_backward(x: torch.Tensor, weight: torch.Tensor, grad_y: torch.Tensor
     x = _dev_f32(x, "x")
     N, C, H, W = x.shape
     w = weight.detach().to(x.device, torch.float32).contiguous()
+    if w.dim() != 4 or w.shape[1] != C or w.shape[2:] != (3, 3):
+        raise ValueError(f"weight must be [O][{C}][3][3], got {tuple(w.shape)}")
     O = w.shape[0]
-    gy = _dev_f32(grad_y, "grad_y")
+    gy =_dev_f32(grad_y, "grad_y")
     if tuple(gy.shape) != (N, O, H, W):
         raise ValueError(f"grad_y must be [{N}][{O}][{H}][{W}], got {tuple(gy.shape)}")
     gx = torch.empty_like(x) if need_x else None
