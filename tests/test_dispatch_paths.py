@@ -1,6 +1,6 @@
 """Every shape-dispatched path of the forward against a float64 reference.
 
-forward_one picks between specialised kernels by image size and batch.  Each
+The forward's stages pick between specialised kernels by image size and batch.  Each
 case below is the smallest shape that reaches one group of those kernels; the
 dispatch path log (kpd_plan_path_log) proves which kernels ran, so a later
 change to a gate cannot move a case onto another kernel unnoticed.
@@ -363,11 +363,13 @@ def test_path_log_is_off_by_default_and_cleared(model_sd):
 
 
 def test_shape_sequence_on_one_plan(model_sd):
-    """One model runs 128 x 96 (B = 2), 250 x 190 (B = 2), 128 x 96 again, then
-    image 1 of the first batch alone: the workspace is re-carved and re-zeroed
-    between shapes, the split-scale slots (sc_dirty) cross a forward that never
-    clears them (250 x 190 is not on the fpn0x path).  Every 128 x 96 output is
-    bit-identical to the first run and to a fresh model's."""
+    """One model runs 128 x 96 (B = 2), 250 x 190 (B = 2), its plan's backbone()
+    at 128 x 96, 128 x 96 again, then image 1 of the first batch alone: the
+    workspace is re-carved and re-zeroed between shapes, the split-scale slots
+    (sc_dirty) cross a forward that never clears them (250 x 190 is not on the
+    fpn0x path) and a backbone() that sets them and runs no top-k to zero them.
+    Every 128 x 96 output is bit-identical to the first run and to a fresh
+    model's."""
     keys = ("keypoints", "visibilities", "heatmap")
     img_a, box_a = _inputs("128x96")
     img_b, box_b = _inputs("250x190")
@@ -385,7 +387,9 @@ def test_shape_sequence_on_one_plan(model_sd):
     m = _model(model_sd, "split")
     first = fwd(m, img_a, box_a)
     fwd(m, img_b, box_b)
-    again = fwd(m, img_a, box_a)
+    m.native_plan(DEV).backbone(img_a.to(DEV))   # fpn0x with every lateral kept, no top-k: the slots stay dirty
+    torch.cuda.synchronize()
+    again =fwd(m, img_a, box_a)
     alone = fwd(m, img_a[1:2], box_a[1:2])
     for k in keys + ("feat0",):
         assert torch.equal(first[k], fresh[k]), f"{k}: first run vs a fresh model"
