@@ -169,6 +169,37 @@ int kpd_preprocess(const uint8_t* src, int height, int width, int channels, int 
                    int tiles_x, int tiles_y, int out_h, int out_w, const float* mean, const float* std, float* dst,
                    void* stream);
 
+/* kpd_preprocess over n images in one call (directory inference: decode on
+ * the host, one batched preprocess, one forward).  srcs / heights / widths /
+ * pitches: host arrays of n entries -- device pointers to uint8 HWC images
+ * that share the channel count `channels`, each with its own size and row
+ * pitch in bytes (any pitch >= width * channels: a strided view needs no
+ * dense copy).  flags, CLAHE parameters, output size, mean and std are shared.
+ * dst: fp32 [n][C'][out_h][out_w], contiguous (device) -- the forward's input.
+ * Image i of dst is bit for bit what kpd_preprocess writes for image i alone:
+ * every stage is integer or contraction-free arithmetic.
+ *
+ * Every stage takes the image index in its grid and reads the image's
+ * geometry from a descriptor table that travels by value in the kernel
+ * arguments, one table per chunk of KPD_PRE_BATCH_CHUNK images: a call issues
+ * one memset (edge pipeline), at most 13 launches per chunk and one
+ * hysteresis launch per four chunks, however many images a chunk holds.  The
+ * Canny hysteresis floods up to 4 * KPD_PRE_BATCH_CHUNK images concurrently,
+ * one workgroup each; the chain behind it (dilate, erode, dilate, erode,
+ * Gaussian 3x3, maximum) is one LDS-tiled kernel.
+ *
+ * Arguments are checked before any device work: the checks of
+ * kpd_preprocess per image (the downscale-factor limit of 31 included), n > 0
+ * and non-null arrays; a failure is KPD_EINVAL and its message names the
+ * first offending image ("image <i>: ...").  Scratch is one stream-ordered
+ * allocation per call (hipMallocAsync, freed on the stream), carved by prefix
+ * sums over the images with 64-bit offsets.  The call does not synchronise
+ * and reads none of the host arrays after it returns. */
+#define KPD_PRE_BATCH_CHUNK 32
+int kpd_preprocess_batch(const uint8_t* const* srcs, const int* heights, const int* widths, const int* pitches,
+                         int n, int channels, int flags, float clip_limit, int tiles_x, int tiles_y, int out_h,
+                         int out_w, const float* mean, const float* std, float* dst, void* stream);
+
 /* Training / evaluation targets: generate_target_heatmap
  * (dll/models/heatmap_head.py:163-224).  kpts: [planes][2] normalised (x, y)
  * (device), out: [planes][H][W] fp32 (device); the (6*int(sigma)+1)^2

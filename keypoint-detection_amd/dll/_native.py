@@ -33,7 +33,8 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_heatmap_head", "kpd_keypoint_head", "kpd_backbone", "kpd_channel_attention", "kpd_decode_heatmaps",
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
-           "kpd_plan_path_log", "kpd_plan_path_query")
+           "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch")
+PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
@@ -90,6 +91,10 @@ def load() -> ctypes.CDLL:
     lib.kpd_target_heatmaps.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
     lib.kpd_keypoint_metrics.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_float),
                                          c_int, c_void_p, c_void_p]
+    lib.kpd_preprocess_batch.argtypes = [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                         ctypes.POINTER(c_int), c_int, c_int, c_int, ctypes.c_float, c_int, c_int,
+                                         c_int, c_int, ctypes.POINTER(ctypes.c_float),
+                                         ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p]
     lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float

@@ -18,7 +18,11 @@ Differences (documented in DESIGN.md):
     model return all-zero keypoints (keypoint_model.py:111-113,123-135).  Here
     the person detector supplies the boxes instead (the
     build-defined glue of PERSON_HEAD + NMS, keypoint_model.py:114-119,
-    person_head.py:96-139); ``--reference-zeros`` keeps the reference's zeros.
+    person_head.py:96-139); ``--reference-zeros`` keeps the reference's zeros;
+  * a directory ``--input`` runs through ``predict_directory`` (:133-160) as one
+    batched device pipeline: host decode, one ``ITransform.batch`` and one
+    forward per mode for every chunk of images, the reference's printout per
+    image.
 Runs on the HIP device (the accelerated path has no CPU fallback).
 """
 from __future__ import annotations
@@ -126,6 +130,104 @@ def predict_single_image(model, image_path, transform, device, gt_path=None, out
     return (keypoints, outputs) if return_outputs else keypoints
 
 
+IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png")
+
+
+def _print_keypoints(outputs):
+    """The reference's printout (:104-129) of one image's outputs."""
+    keypoints = outputs["keypoints"].squeeze().cpu().numpy()
+    print("\nPredicted Keypoints:")
+    print("-" * 40)
+    print(f"Keypoints shape: {keypoints.shape}")
+    if len(keypoints.shape) == 3:
+        keypoints = keypoints[0]
+    for i, name in enumerate(KEYPOINT_NAMES):
+        if i < len(keypoints):
+            x_, y_ = keypoints[i]
+            print(f"{i + 1:2d}. {name:<15} ({x_:.3f}, {y_:.3f})")
+
+
+def _slice_outputs(outputs, i, persons=None):
+    """Image ``i`` of a batch's outputs, cut to its own person count: the
+    shapes of a single-image call."""
+    out = {}
+    for k, v in outputs.items():
+        if isinstance(v, torch.Tensor):
+            v = v[i:i + 1]
+            out[k] = v[:, :persons] if persons is not None and v.dim() >= 2 else v
+        else:   # the per-image box list
+            out[k] = [v[i] if persons is None else v[i][:persons]]
+    return out
+
+
+def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir=None, reference_zeros=False,
+                      batch_size=64):
+    """Reference predict_directory (:133-160) as a batched device pipeline:
+    the images with the reference's extensions, in sorted order, are decoded
+    on the host; every chunk of at most ``batch_size`` is preprocessed by one
+    ``transform.batch`` call and takes one forward per mode.  Images whose
+    label file ``gt_dir/<stem>.txt`` exists form the given-boxes batch, their
+    boxes zero padded to the chunk's largest person count (the forward skips
+    all-zero boxes); the others form the person-detector batch, or the
+    ``bboxes=None`` batch with ``reference_zeros``.  Each image logs its mode
+    and prints the block of ``predict_single_image``.  A file that fails to
+    decode is logged and skipped, as in the reference's try/except.  Returns
+    ``[(path, outputs_i)]`` with the shapes of a single-image call."""
+    from PIL import Image
+    input_dir = Path(input_dir)
+    if output_dir is not None:
+        Path(output_dir).mkdir(parents=True, exist_ok=True)
+    files = sorted(f for f in input_dir.glob("*") if f.suffix.lower() in IMAGE_EXTENSIONS)
+    logging.info(f"Found {len(files)} images in {input_dir}")
+    results = []
+    for c0 in range(0, len(files), max(int(batch_size), 1)):
+        decoded = []   # (path, image, boxes or None)
+        for path in files[c0:c0 + max(int(batch_size), 1)]:
+            try:
+                image = Image.open(path).convert("RGB")
+                gt = Path(gt_dir) / f"{path.stem}.txt" if gt_dir else None
+                boxes = read_gt_boxes(gt, device) if gt is not None and gt.exists() else None
+                if boxes is not None and (boxes.dim() != 2 or boxes.size(0) == 0):
+                    boxes = None   # an empty label file: no caller boxes
+            except Exception as e:
+                logging.error(f"Error processing {path.name}: {e}")
+                continue
+            decoded.append((path, image, boxes))
+        if not decoded:
+            continue
+        x = transform.batch([d[1] for d in decoded]).to(device)
+        given = [i for i, d in enumerate(decoded) if d[2] is not None]
+        other = [i for i, d in enumerate(decoded) if d[2] is None]
+        per_image = {}
+        with torch.no_grad():
+            if given:
+                persons = [decoded[i][2].size(0) for i in given]
+                bt = torch.zeros(len(given), max(persons), 4, device=device)
+                for j, i in enumerate(given):
+                    bt[j, :persons[j]] = decoded[i][2]
+                out = model({"image": x[given] if other else x, "bboxes": bt})
+                for j, i in enumerate(given):
+                    per_image[i] = ("given boxes", _slice_outputs(out, j, persons[j]))
+            if other:
+                xo = x[other] if given else x
+                if reference_zeros:
+                    out, mode = model({"image": xo, "bboxes": None}), "reference zeros (bboxes=None)"
+                else:
+                    out, mode = model({"image": xo}), "person detector"
+                for j, i in enumerate(other):
+                    per_image[i] = (mode, _slice_outputs(out, j))
+        for i, (path, _, _) in enumerate(decoded):
+            mode, outputs = per_image[i]
+            logging.info(f"{path.name}: boxes from {mode}")
+            if mode == "person detector":
+                kept = int((outputs["box_scores"][0] > 0).sum())
+                logging.info(f"detector kept {kept} person(s); person 0 box (cx, cy, w, h) = "
+                             f"{[round(float(v), 4) for v in outputs['boxes'][0][0]]}")
+            _print_keypoints(outputs)
+            results.append((path, outputs))
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Predict keypoints in images")
     ap.add_argument("--config", required=True)
@@ -158,11 +260,8 @@ def main(argv=None):
         results.append((inp, predict_single_image(model, inp, transform, device, gt if gt and gt.is_file() else None,
                                                   reference_zeros=args.reference_zeros, return_outputs=True)[1]))
     else:
-        for img in sorted(inp.glob("*.*")):
-            if img.suffix.lower() in (".jpg", ".jpeg", ".png"):
-                out = predict_single_image(model, img, transform, device, (gt / f"{img.stem}.txt") if gt else None,
-                                           reference_zeros=args.reference_zeros, return_outputs=True)[1]
-                results.append((img, out))
+        results = predict_directory(model, inp, transform, device, args.output, gt_dir=gt,
+                                    reference_zeros=args.reference_zeros)
     logging.info("Prediction completed successfully!")
     return {"model": model, "results": results}
 
