@@ -200,6 +200,61 @@ int kpd_preprocess_batch(const uint8_t* const* srcs, const int* heights, const i
                          int n, int channels, int flags, float clip_limit, int tiles_x, int tiles_y, int out_h,
                          int out_w, const float* mean, const float* std, float* dst, void* stream);
 
+/* Pose overlays on the device: person boxes, skeleton limbs,
+ * joints and an optional heatmap underlay drawn in place onto n uint8 HWC RGB
+ * images, straight from a forward's output tensors.  What the CLI's
+ * "Saved visualization to ..." promises (reference scripts/predict.py:86-131,
+ * which imports a drawing function its package never defines).
+ *   images / heights / widths / pitches: host arrays of n entries -- device
+ *       pointers to 3-channel images, each with its own size (sides <=
+ *       KPD_DRAW_MAX_SIDE) and row pitch in bytes, pitch >= 3 * width; no byte
+ *       outside [row, row + 3 * width) of any row is written, so a column
+ *       slice of a wider tensor is drawn in place.
+ *   keypoints    [n][P][K][2] fp32 normalised image coordinates (device): the
+ *                memory of the forward's [n][P][1][K][2];
+ *   visibilities [n][P][K][3] fp32 one-hot (device);
+ *   boxes        [n][P][4] fp32 cxcywh normalised (device), or NULL;
+ *   heatmap      [n][P][K][hh][hw] fp32 (device), or NULL; hh, hw <= KPD_DRAW_MAX_HEAT.
+ *   limbs [L][2] joint indices, limb_colors [L][3], joint_colors [3][3] (one
+ *   RGB colour per visibility class), box_color [3]: host tables.
+ *   joint_radius, limb_half_width, box_half_width: 1/16-pixel units, each in
+ *   [0, KPD_DRAW_MAX_WIDTH]; alpha, heat_alpha in [0, 256]; min_class in
+ *   {0, 1, 2}: joints of a lower visibility class are not drawn.
+ *   flags: KPD_DRAW_* layers.  KPD_DRAW_BOXES and KPD_DRAW_HEAT need boxes,
+ *   KPD_DRAW_HEAT needs heatmap.  K in [1, 32], L in [0, 64], P >= 1.
+ * The drawing rules are integer arithmetic on a 16-subpixel grid and are
+ * written out in DESIGN.md §3b; tests/draw_ref.py restates them in numpy and
+ * the result is bit-equal.  Image i's result does not depend on the images it
+ * is drawn with.
+ *
+ * A setup kernel writes one 64-byte record per (image, person, primitive);
+ * one 256-thread workgroup per KPD_DRAW_TILE_W x KPD_DRAW_TILE_H tile culls
+ * the image's records against the tile in blocks of 256, in record order, and
+ * blends the survivors into pixels held in registers; a tile nothing touches
+ * is neither loaded nor stored.  Images are addressed through a descriptor
+ * table passed by value, one table (two launches) per chunk of KPD_DRAW_CHUNK
+ * images; the heat layer adds one launch per call.
+ *
+ * Arguments are checked before any device work; a failure is KPD_EINVAL and
+ * per-image failures read "image <i>: ...".  Scratch is one stream-ordered
+ * allocation per call.  The call does not synchronise and reads no host
+ * array after it returns (the tables travel in the kernel arguments). */
+#define KPD_DRAW_BOXES 1
+#define KPD_DRAW_LIMBS 2
+#define KPD_DRAW_JOINTS 4
+#define KPD_DRAW_HEAT 8
+#define KPD_DRAW_CHUNK 32      /* images per descriptor table */
+#define KPD_DRAW_TILE_W 64     /* pixels of one workgroup's tile */
+#define KPD_DRAW_TILE_H 16
+#define KPD_DRAW_MAX_SIDE 16384
+#define KPD_DRAW_MAX_WIDTH 512 /* 32 px in 1/16-pixel units */
+#define KPD_DRAW_MAX_HEAT 1024
+int kpd_draw_poses(uint8_t* const* images, const int* heights, const int* widths, const int* pitches, int n,
+                   const float* keypoints, const float* visibilities, const float* boxes, const float* heatmap,
+                   int P, int K, int hh, int hw, const int* limbs, int L, const uint8_t* limb_colors,
+                   const uint8_t* joint_colors, const uint8_t* box_color, int joint_radius, int limb_half_width,
+                   int box_half_width, int alpha, int heat_alpha, int min_class, int flags, void* stream);
+
 /* Training / evaluation targets: generate_target_heatmap
  * (dll/models/heatmap_head.py:163-224).  kpts: [planes][2] normalised (x, y)
  * (device), out: [planes][H][W] fp32 (device); the (6*int(sigma)+1)^2

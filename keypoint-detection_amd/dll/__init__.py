@@ -1,7 +1,12 @@
 """MI355X-native drop-in for the reference's ``dll`` inference path.
 
-Only the hot path (``dll.models`` + configs) is provided; the reference's
-data pipeline, training loop and visualisation are out of scope.
+The hot path (``dll.models`` + configs) with what stands around it on the
+device: ``dll.data`` (``ITransform``, the YOLO-pose dataset and its targets),
+``dll.losses``, ``dll.ops`` and ``dll.utils`` (metrics and ``draw_poses``, the
+pose overlay the prediction CLI saves: boxes, skeleton, joints and a heatmap
+underlay drawn in place by ``kpd_draw_poses``).  The training loop, the
+augmentations, feature-map plotting and the reference's matplotlib panels are
+out of scope.
 """
 from .configs import ModelConfig, TrainingConfig
 from .models import MultiPersonKeypointModel

@@ -33,8 +33,16 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_heatmap_head", "kpd_keypoint_head", "kpd_backbone", "kpd_channel_attention", "kpd_decode_heatmaps",
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
-           "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch")
+           "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
+# kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
+DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
+DRAW_CHUNK = 32        # KPD_DRAW_CHUNK
+DRAW_TILE_W = 64       # KPD_DRAW_TILE_W
+DRAW_TILE_H = 16       # KPD_DRAW_TILE_H
+DRAW_MAX_SIDE = 16384  # KPD_DRAW_MAX_SIDE
+DRAW_MAX_WIDTH = 512   # KPD_DRAW_MAX_WIDTH: 32 px in 1/16-pixel units
+DRAW_MAX_HEAT = 1024   # KPD_DRAW_MAX_HEAT
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
@@ -95,6 +103,11 @@ def load() -> ctypes.CDLL:
                                          ctypes.POINTER(c_int), c_int, c_int, c_int, ctypes.c_float, c_int, c_int,
                                          c_int, c_int, ctypes.POINTER(ctypes.c_float),
                                          ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lib.kpd_draw_poses.argtypes = [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                   ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, u8p, u8p, u8p,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float

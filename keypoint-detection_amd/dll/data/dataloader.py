@@ -382,3 +382,31 @@ def create_adaptive_dataloader(dataset_dir: str, batch_size: int = 32, num_worke
     return DataLoader(ds, batch_sampler=AdaptiveBatchSampler(ds, batch_size, max_persons_per_batch),
                       num_workers=nw, pin_memory=False, collate_fn=efficient_collate_fn,
                       persistent_workers=nw > 0)
+
+
+def visualize_keypoints_multi_person(image, keypoints, visibilities=None, bboxes=None, save_path=None):
+    """The drawing function the reference's CLI imports from this module
+    (scripts/predict.py:18) and its package never defines: person boxes,
+    skeleton and joints drawn over ``image`` on the device
+    (``dll.utils.draw_poses``).  ``keypoints`` [P, K, 2] (or [K, 2])
+    normalised, ``visibilities`` [P, K] classes or [P, K, 3] one-hot (default:
+    all visible), ``bboxes`` [P, 4] cxcywh normalised (default: no boxes,
+    every person drawn).  Returns the uint8 [H, W, 3] array and saves it to
+    ``save_path`` when given."""
+    from ..utils.draw import DEFAULT_LAYERS, draw_poses
+    device = keypoints.device if isinstance(keypoints, torch.Tensor) and keypoints.is_cuda else torch.device("cuda")
+    kp = torch.as_tensor(keypoints, dtype=torch.float32).to(device)
+    kp = kp.reshape(1, -1, kp.shape[-2], 2)
+    outputs = {"keypoints": kp}
+    if visibilities is not None:
+        outputs["visibilities"] = torch.as_tensor(visibilities).to(device)
+    if bboxes is not None:
+        outputs["boxes"] = torch.as_tensor(bboxes, dtype=torch.float32).to(device).reshape(1, -1, 4)
+        # rows here line up with the keypoints as given (no forward has compacted them): scores keep the slots
+        outputs["box_scores"] = torch.ones(1, outputs["boxes"].shape[1], device=device)
+    layers = tuple(name for name in DEFAULT_LAYERS if name != "boxes" or bboxes is not None)
+    out = draw_poses([image], outputs, layers=layers)[0].cpu().numpy()
+    if save_path is not None:
+        from PIL import Image
+        Image.fromarray(out).save(save_path)
+    return out

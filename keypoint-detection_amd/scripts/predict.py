@@ -22,7 +22,13 @@ Differences (documented in DESIGN.md):
   * a directory ``--input`` runs through ``predict_directory`` (:133-160) as one
     batched device pipeline: host decode, one ``ITransform.batch`` and one
     forward per mode for every chunk of images, the reference's printout per
-    image.
+    image;
+  * the reference logs "Saved visualization to ..." and writes nothing (its
+    drawing import does not resolve).  Here every image leaves two files in
+    ``--output``: ``<stem>_keypoints<suffix>``, the overlay (boxes, skeleton,
+    joints) drawn on the device at the image's own resolution
+    (``dll.utils.draw_poses``, one call per forward), and
+    ``<stem>_keypoints.txt``, the prediction as YOLO-pose label lines.
 Runs on the HIP device (the accelerated path has no CPU fallback).
 """
 from __future__ import annotations
@@ -40,6 +46,7 @@ from dll.configs import (BackboneConfig, KeypointHeadConfig, ModelConfig,  # noq
                          PersonDetectionConfig, TrainingConfig)
 from dll.data import ITransform  # noqa: E402
 from dll.models import MultiPersonKeypointModel  # noqa: E402
+from dll.utils import draw_poses, format_pose_labels  # noqa: E402
 
 KEYPOINT_NAMES = ["nose", "left_eye", "right_eye", "left_ear", "right_ear", "left_shoulder", "right_shoulder",
                   "left_elbow", "right_elbow", "left_wrist", "right_wrist", "left_hip", "right_hip", "left_knee",
@@ -96,13 +103,34 @@ def read_gt_boxes(gt_path, device):
     return torch.tensor(boxes, device=device)
 
 
+def output_path_for(output_dir, image_path):
+    """``<output_dir>/<stem>_keypoints<suffix>`` (reference :146, :195, :210)."""
+    image_path = Path(image_path)
+    return Path(output_dir) / f"{image_path.stem}_keypoints{image_path.suffix}"
+
+
+def save_prediction(drawn, outputs, output_path):
+    """Write one image's two files: the overlay ``drawn`` (uint8 [H, W, 3]
+    device tensor at the image's own resolution -- the one host copy) to
+    ``output_path`` and the prediction as YOLO-pose label text
+    (``dll.utils.format_pose_labels``) beside it as ``<stem>_keypoints.txt``."""
+    from PIL import Image
+    output_path = Path(output_path)
+    output_path.parent.mkdir(parents=True, exist_ok=True)
+    Image.fromarray(drawn.cpu().numpy()).save(output_path)
+    output_path.with_suffix(".txt").write_text(format_pose_labels(outputs))
+
+
 def predict_single_image(model, image_path, transform, device, gt_path=None, output_path=None,
                          reference_zeros=False, return_outputs=False):
     """Reference predict_single_image (:64-131).  Without a GT file the
     detector branch runs (``model({'image': x})``: no 'bboxes' key), unless
-    ``reference_zeros`` asks for the reference's ``bboxes=None`` call."""
+    ``reference_zeros`` asks for the reference's ``bboxes=None`` call.  With
+    ``output_path`` the overlay (drawn on the device, ``dll.utils.draw_poses``)
+    and the label file are written (``save_prediction``)."""
     from PIL import Image
-    x = transform(Image.open(image_path).convert("RGB")).unsqueeze(0).to(device)
+    image = Image.open(image_path).convert("RGB")
+    x = transform(image).unsqueeze(0).to(device)
     bboxes = read_gt_boxes(gt_path, device) if gt_path and Path(gt_path).exists() else None
     if bboxes is not None:
         batch, mode = {"image": x, "bboxes": bboxes.unsqueeze(0)}, "given boxes"
@@ -113,6 +141,8 @@ def predict_single_image(model, image_path, transform, device, gt_path=None, out
     logging.info(f"{Path(image_path).name}: boxes from {mode}")
     with torch.no_grad():
         outputs = model(batch)
+    if output_path is not None:
+        save_prediction(draw_poses([image], outputs)[0], outputs, output_path)
     if bboxes is None and not reference_zeros:
         n = int((outputs["box_scores"][0] > 0).sum())
         logging.info(f"detector kept {n} person(s); person 0 box (cx, cy, w, h) = "
@@ -171,7 +201,10 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
     all-zero boxes); the others form the person-detector batch, or the
     ``bboxes=None`` batch with ``reference_zeros``.  Each image logs its mode
     and prints the block of ``predict_single_image``.  A file that fails to
-    decode is logged and skipped, as in the reference's try/except.  Returns
+    decode is logged and skipped, as in the reference's try/except.  With an
+    ``output_dir`` every forward's batched outputs are drawn onto its images by
+    one ``draw_poses`` call and each image's overlay and label file are written
+    (``save_prediction``).  Returns
     ``[(path, outputs_i)]`` with the shapes of a single-image call."""
     from PIL import Image
     input_dir = Path(input_dir)
@@ -198,7 +231,12 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
         x = transform.batch([d[1] for d in decoded]).to(device)
         given = [i for i, d in enumerate(decoded) if d[2] is not None]
         other = [i for i, d in enumerate(decoded) if d[2] is None]
-        per_image = {}
+        per_image, drawn = {}, {}
+
+        def draw(indices, out):   # one draw call per forward, on its batched outputs, at the original resolutions
+            if output_dir is not None:
+                drawn.update(zip(indices, draw_poses([decoded[i][1] for i in indices], out)))
+
         with torch.no_grad():
             if given:
                 persons = [decoded[i][2].size(0) for i in given]
@@ -206,6 +244,7 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
                 for j, i in enumerate(given):
                     bt[j, :persons[j]] = decoded[i][2]
                 out = model({"image": x[given] if other else x, "bboxes": bt})
+                draw(given, out)
                 for j, i in enumerate(given):
                     per_image[i] = ("given boxes", _slice_outputs(out, j, persons[j]))
             if other:
@@ -214,6 +253,7 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
                     out, mode = model({"image": xo, "bboxes": None}), "reference zeros (bboxes=None)"
                 else:
                     out, mode = model({"image": xo}), "person detector"
+                draw(other, out)
                 for j, i in enumerate(other):
                     per_image[i] = (mode, _slice_outputs(out, j))
         for i, (path, _, _) in enumerate(decoded):
@@ -224,6 +264,10 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
                 logging.info(f"detector kept {kept} person(s); person 0 box (cx, cy, w, h) = "
                              f"{[round(float(v), 4) for v in outputs['boxes'][0][0]]}")
             _print_keypoints(outputs)
+            if output_dir is not None:
+                output_path = output_path_for(output_dir, path)
+                save_prediction(drawn[i], outputs, output_path)
+                logging.info(f"Saved visualization to {output_path}")
             results.append((path, outputs))
     return results
 
@@ -257,8 +301,11 @@ def main(argv=None):
     logging.info(f"precision {args.precision}")
     results = []
     if inp.is_file():
+        output_path = output_path_for(args.output, inp)
         results.append((inp, predict_single_image(model, inp, transform, device, gt if gt and gt.is_file() else None,
-                                                  reference_zeros=args.reference_zeros, return_outputs=True)[1]))
+                                                  output_path=output_path, reference_zeros=args.reference_zeros,
+                                                  return_outputs=True)[1]))
+        logging.info(f"Saved visualization to {output_path}")
     else:
         results = predict_directory(model, inp, transform, device, args.output, gt_dir=gt,
                                     reference_zeros=args.reference_zeros)
