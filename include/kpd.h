@@ -271,6 +271,61 @@ int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, float sigma
 int kpd_keypoint_metrics(const float* pred, const float* gt, const float* vis, long n, const float* thresholds,
                          int n_thresholds, float* out, void* stream);
 
+/* COCO keypoint matching on the device: object keypoint
+ * similarity (OKS) of every detection / ground-truth pair of B images and
+ * COCOeval's greedy matching at T OKS thresholds (computeOks / evaluateImg for
+ * keypoints at area range "all"; crowd annotations are not modelled).  The
+ * per-batch half of keypoint AP: the dataset-level accumulation over the
+ * outputs is a handful of tensor ops (dll/utils/oks.py).
+ *   pred_kpts   [B][D][K][2] fp32 (device): the memory of a forward's
+ *               [B][D][1][K][2];
+ *   pred_scores [B][D] fp32 (device): a slot whose score is not > 0 (a NaN
+ *               too) is absent;
+ *   gt_kpts [B][G][K][2], gt_vis [B][G][K] (> 0 = labelled), gt_boxes
+ *   [B][G][4] cxcywh in the keypoints' units, gt_area [B][G] in scaled units
+ *   squared, n_gt [B] int32 (the valid ground truths of image b are slots
+ *   0 .. n_gt[b]-1, clamped to [0, G]), scale [B][2] = (sx, sy), multiplied
+ *   onto every x / y before differencing: all device;
+ *   sigmas [K], thresholds [T]: host arrays (they travel in the kernel
+ *   arguments, the call reads neither after it returns).
+ * Rules.  var_k = (2 sigma_k)^2; k1 = the gt's labelled keypoints.  With
+ * k1 > 0, dx = sx xd - sx xg over the labelled k; with k1 == 0 the gt is
+ * ignored and every k measures the distance to the gt box doubled about its
+ * centre (x0 = (cx - w/2) sx - w sx, x1 = (cx - w/2) sx + 2 w sx, dx =
+ * max(0, x0 - sx xd) + max(0, sx xd - x1)).  e_k = (dx^2 + dy^2) / var_k /
+ * (area + 2^-52) / 2 and OKS = mean of exp(-e_k) over the counted k, all in
+ * double from the fp32 inputs.  Detections are ranked by score descending,
+ * ties to the lower slot, the first M = min(max_dets, D) present ones kept;
+ * ground truths are ordered counted ones first, each group in slot order.  Per
+ * threshold t and detection in rank order: best = min(t, 1 - 1e-10); walking
+ * the gts, one already matched at t is skipped, the walk stops at an ignored
+ * gt once a counted one is held, a gt with OKS < best is skipped, any other
+ * becomes the match and its OKS the new best (an equal OKS replaces).
+ * Outputs (device):
+ *   oks        [B][D][G] double, caller's slot order, 0 for an absent
+ *              detection or a slot past n_gt; may be NULL;
+ *   det_score  [B][M] scores in rank order, 0 past n_det;
+ *   det_slot   [B][M] int32 caller slot at each rank, -1 past n_det;
+ *   det_match  [B][T][M] int32 matched gt slot (caller order) or -1;
+ *   det_ignore [B][T][M] uint8: the matched gt is an ignored one;
+ *   gt_match   [B][T][G] int32 matched detection slot or -1;
+ *   counts     [B][2] int32: n_det (ranked, <= M), n_gt_counted.
+ * Inputs of present detections and valid ground truths are expected finite.
+ * One launch, one workgroup per image: the OKS matrix in LDS, one wave per
+ * threshold.  Arguments are checked before any device work (KPD_EINVAL, the
+ * message names the argument); B = 0 returns KPD_OK without a launch; D = 0
+ * or G = 0 is valid, and an array of zero elements may then be NULL.  The
+ * call does not synchronise.  tests/oks_ref.py restates the rules in numpy. */
+#define KPD_OKS_MAX_K 32
+#define KPD_OKS_MAX_T 16
+#define KPD_OKS_MAX_D 64
+#define KPD_OKS_MAX_G 64
+int kpd_oks_match(const float* pred_kpts, const float* pred_scores, const float* gt_kpts, const float* gt_vis,
+                  const float* gt_boxes, const float* gt_area, const int32_t* n_gt, const float* scale,
+                  const float* sigmas, const float* thresholds, int B, int D, int G, int K, int T, int max_dets,
+                  double* oks, float* det_score, int32_t* det_slot, int32_t* det_match, uint8_t* det_ignore,
+                  int32_t* gt_match, int32_t* counts, void* stream);
+
 /* Training loss: AdaptiveHeatmapLoss.forward
  * (dll/losses/keypoint_loss.py:202-280).  pred, gt: [B][K][H][W] fp32,
  * target_weight: [B][K] or NULL (all device).  Threshold = clamp(torch.quantile(

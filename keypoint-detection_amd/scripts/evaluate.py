@@ -1,16 +1,27 @@
 #!/usr/bin/env python3
-"""Real-data PCK / ADE evaluation on a YOLO-pose split, end to end on the
-device: decode (host) -> ITransform + target heatmaps (kpd_preprocess,
-kpd_target_heatmaps) -> collate -> MultiPersonKeypointModel with the
-ground-truth boxes (kpd_forward) -> ADE / PCK (kpd_keypoint_metrics).
+"""Real-data evaluation on a YOLO-pose split, end to end on the device:
+decode (host) -> ITransform + target heatmaps (kpd_preprocess,
+kpd_target_heatmaps) -> collate -> MultiPersonKeypointModel (kpd_forward) ->
+metrics.
 
-The metrics are the reference's validation metrics
-(dll/training/trainer.py:384-429), averaged over batches as its
-validate_epoch does (:305-395); the loss terms are not computed (training is
-out of scope).
+``--metric pck`` (the default): ADE / PCK (kpd_keypoint_metrics), the
+reference's validation metrics (dll/training/trainer.py:384-429), averaged
+over batches as its validate_epoch does (:305-395); the loss terms are not
+computed (training is out of scope).  They compare prediction slot p with
+ground-truth slot p, so they are defined only with the ground-truth boxes.
+
+``--metric oks``: COCO keypoint AP / AP50 / AP75 / AR (kpd_oks_match per batch,
+``dll.utils.OksEvaluator``), which matches predicted poses to labelled persons
+and therefore also scores ``--boxes detector``, the model's own person
+detector (``model({"image": x})``).  ``--metric both`` prints both sets.
+
+The loader's ``efficient_collate_fn`` drops images without a labelled person
+from a batch, so detections on such images are not counted as false
+positives (inherited behaviour).
 
     python scripts/evaluate.py --config configs/default_config.yaml \
-        --model best_model.pth --dataset-dir data/ --split val --batch-size 32
+        --model best_model.pth --dataset-dir data/ --split val --batch-size 32 \
+        [--boxes detector --metric oks]
 """
 from __future__ import annotations
 
@@ -26,23 +37,37 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from dll.data import create_optimized_dataloader  # noqa: E402
-from dll.utils import calculate_validation_metrics  # noqa: E402
+from dll.utils import OksEvaluator, calculate_validation_metrics  # noqa: E402
 from predict import load_config, load_model, setup_logging  # noqa: E402
 
 
-def evaluate(model, loader, pck_thresholds):
-    sums, n = defaultdict(float), 0
+def evaluate(model, loader, pck_thresholds, boxes="gt", oks=None):
+    """One pass over ``loader``.  ``pck_thresholds`` None skips ADE / PCK;
+    ``oks`` (an ``OksEvaluator``) is updated per batch, on the device.  Returns
+    (metrics, batches) or, with ``oks``, (metrics, batches, images)."""
+    sums, n, images = defaultdict(float), 0, 0
     with torch.no_grad():
         for batch in loader:
-            out = model({"image": batch["image"], "bboxes": batch["bboxes"]})
-            for k, v in calculate_validation_metrics(out, batch, pck_thresholds).items():
-                sums[k] += v
+            inp = {"image": batch["image"]}
+            if boxes == "gt":
+                inp["bboxes"] = batch["bboxes"]
+            out = model(inp)
+            if pck_thresholds is not None:
+                for k, v in calculate_validation_metrics(out, batch, pck_thresholds).items():
+                    sums[k] += v
+            if oks is not None:
+                oks.update(out, batch)
+                images += batch["image"].shape[0]
             n += 1
-    return {k: v / max(n, 1) for k, v in sums.items()}, n
+    metrics = {k: v / max(n, 1) for k, v in sums.items()}
+    if oks is None:
+        return metrics, n
+    metrics.update(oks.summarize())
+    return metrics, n, images
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Evaluate keypoint PCK / ADE on a dataset split")
+    ap = argparse.ArgumentParser(description="Evaluate keypoint PCK / ADE or COCO OKS AP on a dataset split")
     ap.add_argument("--config", required=True)
     ap.add_argument("--model", required=True, help="checkpoint path, or 'synthetic'")
     ap.add_argument("--dataset-dir", required=True)
@@ -50,7 +75,14 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--precision", default="split", choices=["split", "fp32", "mixed"])
+    ap.add_argument("--boxes", default="gt", choices=["gt", "detector"],
+                    help="person boxes: the labels' (gt) or the model's person detector")
+    ap.add_argument("--metric", default="pck", choices=["pck", "oks", "both"],
+                    help="pck: slot-wise ADE / PCK; oks: COCO keypoint AP / AP50 / AP75 / AR; both")
     args = ap.parse_args(argv)
+    if args.boxes == "detector" and args.metric != "oks":
+        ap.error("ADE / PCK compare prediction slot p with ground-truth slot p and are not defined for detector "
+                 "boxes, which have their own order and count: use --boxes detector --metric oks")
     setup_logging()
     cfg = load_config(args.config)
     device = torch.device(args.device)
@@ -60,8 +92,13 @@ def main(argv=None):
                                          img_size=bcfg["input_size"], grayscale=bcfg.get("in_channels", 3) == 1,
                                          device=device)
     model = load_model(args.model, cfg, device, args.precision)
-    metrics, n = evaluate(model, loader, thresholds)
-    print(json.dumps({"split": args.split, "batches": n, **metrics}))
+    if args.metric == "pck":
+        metrics, n = evaluate(model, loader, thresholds)
+        print(json.dumps({"split": args.split, "batches": n, **metrics}))
+        return metrics
+    metrics, n, images = evaluate(model, loader, thresholds if args.metric == "both" else None, boxes=args.boxes,
+                                  oks=OksEvaluator())
+    print(json.dumps({"split": args.split, "batches": n, "boxes": args.boxes, "images": images, **metrics}))
     return metrics
 
 
