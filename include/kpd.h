@@ -326,6 +326,65 @@ int kpd_oks_match(const float* pred_kpts, const float* pred_scores, const float*
                   double* oks, float* det_score, int32_t* det_slot, int32_t* det_match, uint8_t* det_ignore,
                   int32_t* gt_match, int32_t* counts, void* stream);
 
+/* OKS pose-NMS on the device: the step of a top-down pose
+ * pipeline between scoring and evaluation or drawing.  A pose whose object
+ * keypoint similarity with a higher-scoring pose of the same image is too high
+ * is suppressed (hard) or has its score decayed (soft).
+ *   kpts   [B][D][K][2] fp32 (device): the memory of a forward's
+ *          [B][D][1][K][2];
+ *   scores [B][D] fp32 (device): a slot whose score is not > 0 (a NaN too) is
+ *          absent;
+ *   area   [B][D] in scaled units squared, kconf [B][D][K] per-keypoint
+ *          confidence or NULL, scale [B][2] = (sx, sy), multiplied onto every
+ *          x / y before differencing: all device;
+ *   sigmas [K]: a host array (it travels in the kernel arguments, the call
+ *          does not read it after it returns).
+ * Rules, all in double from the fp32 inputs.  Pair OKS of present poses
+ * i != j: den = (area_i + area_j) / 2 + 2^-52; keypoint k counts when kconf is
+ * NULL or kconf_i[k] > vis_threshold and kconf_j[k] > vis_threshold; dx =
+ * sx x_i - sx x_j, dy likewise; e_k = (dx^2 + dy^2) / (2 sigma_k)^2 / den / 2;
+ * OKS = mean of exp(-e_k) over the counted k, 0 when none counts.  Pairs i < j
+ * are computed and mirrored (the matrix is bit-symmetric); a pair with an
+ * absent pose and the diagonal are 0.  Present poses are ranked by score
+ * descending, ties to the lower slot.  threshold, vis_threshold and min_score
+ * enter as the fp32 values passed.
+ *   KPD_POSE_NMS_HARD: walking the ranks, the walk ends at the first pose whose
+ *   score is not > min_score or once max_keep poses are kept; a pose whose OKS
+ *   with an already kept pose is > threshold is suppressed (suppressed_by =
+ *   the earliest-kept such pose); any other is kept with its input score.
+ *   KPD_POSE_NMS_SOFT (Gaussian) / KPD_POSE_NMS_SOFT_LINEAR: current scores
+ *   start as the input scores.  Repeat: take the remaining pose with the
+ *   highest current score (ties to the lower slot); stop if that score is not
+ *   > min_score or max_keep poses have been picked; keep it with its current
+ *   score; multiply every remaining pose's current score by exp(-o^2 /
+ *   threshold) (Gaussian), or by 1 - o if o >= threshold else 1 (linear), o
+ *   its OKS with the pick.
+ * Outputs (device):
+ *   oks           [B][D][D] double, may be NULL;
+ *   keep          [B][D] int32 caller slots in keep order, -1 past n_keep;
+ *   n_keep        [B] int32;
+ *   scores_out    [B][D] fp32 in caller slot order: the kept pose's score cast
+ *                 to fp32, 0 for a suppressed, unpicked or absent slot;
+ *   suppressed_by [B][D] int32 slot of the suppressing pose or -1 (always -1
+ *                 in the soft modes).
+ * Inputs of present poses are expected finite.  One launch, one workgroup per
+ * image (an image's result does not depend on the others of the call): the OKS
+ * matrix in LDS, the suppression on one wave.  Arguments are checked before
+ * any device work (KPD_EINVAL, the message names the argument): D in [0,
+ * KPD_POSE_NMS_MAX_D], K in [1, KPD_POSE_NMS_MAX_K], threshold in (0, 1],
+ * max_keep >= 1; B = 0 returns KPD_OK without a launch; D = 0 is valid, and an
+ * array of zero elements may then be NULL.  The call does not synchronise.
+ * tests/pose_nms_ref.py restates the rules in numpy. */
+#define KPD_POSE_NMS_MAX_D 64
+#define KPD_POSE_NMS_MAX_K 32
+#define KPD_POSE_NMS_HARD 0
+#define KPD_POSE_NMS_SOFT 1
+#define KPD_POSE_NMS_SOFT_LINEAR 2
+int kpd_pose_nms(const float* kpts, const float* scores, const float* area, const float* kconf, const float* scale,
+                 const float* sigmas, int B, int D, int K, int mode, float threshold, float vis_threshold,
+                 float min_score, int max_keep, double* oks, int32_t* keep, int32_t* n_keep, float* scores_out,
+                 int32_t* suppressed_by, void* stream);
+
 /* Training loss: AdaptiveHeatmapLoss.forward
  * (dll/losses/keypoint_loss.py:202-280).  pred, gt: [B][K][H][W] fp32,
  * target_weight: [B][K] or NULL (all device).  Threshold = clamp(torch.quantile(

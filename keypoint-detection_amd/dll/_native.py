@@ -34,7 +34,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
-           "kpd_oks_match")
+           "kpd_oks_match", "kpd_pose_nms")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -49,6 +49,10 @@ OKS_MAX_K = 32         # KPD_OKS_MAX_K: keypoints per pose
 OKS_MAX_T = 16         # KPD_OKS_MAX_T: OKS thresholds, one wave each
 OKS_MAX_D = 64         # KPD_OKS_MAX_D: detection slots per image
 OKS_MAX_G = 64         # KPD_OKS_MAX_G: ground-truth slots per image
+# kpd_pose_nms (include/kpd.h): limits of one call and the suppression modes
+POSE_NMS_MAX_D = 64    # KPD_POSE_NMS_MAX_D: pose slots per image, one lane each
+POSE_NMS_MAX_K = 32    # KPD_POSE_NMS_MAX_K: keypoints per pose
+POSE_NMS_HARD, POSE_NMS_SOFT, POSE_NMS_SOFT_LINEAR = 0, 1, 2
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
@@ -116,6 +120,8 @@ def load() -> ctypes.CDLL:
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.kpd_oks_match.argtypes = [c_void_p] * 8 + [ctypes.POINTER(ctypes.c_float)] * 2 + [c_int] * 6 + \
         [c_void_p] * 8
+    lib.kpd_pose_nms.argtypes = [c_void_p] * 5 + [ctypes.POINTER(ctypes.c_float)] + [c_int] * 4 + \
+        [ctypes.c_float] * 3 + [c_int] + [c_void_p] * 6
     lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float

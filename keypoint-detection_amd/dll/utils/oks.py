@@ -98,6 +98,19 @@ def oks_match(pred_kpts: torch.Tensor, pred_scores: torch.Tensor, gt_kpts: torch
     return out
 
 
+def keypoint_peaks(outputs: Dict) -> torch.Tensor:
+    """The maximum of every heatmap plane of a forward's ``outputs``, [B, P, K]:
+    one confidence per keypoint (``outputs['heatmap']`` is a sigmoid)."""
+    k = torch.as_tensor(outputs["keypoints"])
+    B, dev = k.shape[0], k.device
+    P = keypoints_tensor(outputs, B).shape[1]
+    heat = outputs.get("heatmap")
+    if heat is None:
+        raise ValueError("the keypoint peaks need outputs['heatmap']")
+    heat = torch.as_tensor(heat).to(dev, torch.float32)
+    return heat.reshape(B, P, -1, heat.shape[-2] * heat.shape[-1]).amax(-1)
+
+
 def pose_scores(outputs: Dict, rescore: bool = True) -> torch.Tensor:
     """One score per person slot of a forward's ``outputs``, [B, P].  The base
     is the detector's ``box_scores`` when the outputs carry them; otherwise 1
@@ -116,12 +129,9 @@ def pose_scores(outputs: Dict, rescore: bool = True) -> torch.Tensor:
         base = torch.ones(B, P, device=dev) if boxes is None else (boxes != 0).any(-1).to(torch.float32)
     if not rescore:
         return base
-    heat = outputs.get("heatmap")
-    if heat is None:
+    if outputs.get("heatmap") is None:
         raise ValueError("rescore=True needs outputs['heatmap']")
-    heat = torch.as_tensor(heat).to(dev, torch.float32)
-    peak = heat.reshape(B, P, -1, heat.shape[-2] * heat.shape[-1]).amax(-1)   # [B, P, K]
-    return base * peak.mean(-1)
+    return base * keypoint_peaks(outputs).mean(-1)
 
 
 class OksEvaluator:

@@ -15,13 +15,18 @@ ground-truth slot p, so they are defined only with the ground-truth boxes.
 and therefore also scores ``--boxes detector``, the model's own person
 detector (``model({"image": x})``).  ``--metric both`` prints both sets.
 
+``--pose-nms hard|soft|soft-linear`` (with ``--metric oks`` or ``both``) puts
+OKS pose-NMS (kpd_pose_nms, ``dll.utils.suppress_poses``) between the forward
+and the OKS matching: two boxes on one person no longer count as a true and a
+false positive.  ADE / PCK are slot-wise and keep the unsuppressed outputs.
+
 The loader's ``efficient_collate_fn`` drops images without a labelled person
 from a batch, so detections on such images are not counted as false
 positives (inherited behaviour).
 
     python scripts/evaluate.py --config configs/default_config.yaml \
         --model best_model.pth --dataset-dir data/ --split val --batch-size 32 \
-        [--boxes detector --metric oks]
+        [--boxes detector --metric oks [--pose-nms hard]]
 """
 from __future__ import annotations
 
@@ -37,14 +42,17 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from dll.data import create_optimized_dataloader  # noqa: E402
-from dll.utils import OksEvaluator, calculate_validation_metrics  # noqa: E402
-from predict import load_config, load_model, setup_logging  # noqa: E402
+from dll.utils import OksEvaluator, calculate_validation_metrics, suppress_poses  # noqa: E402
+from predict import (add_pose_nms_arguments, load_config, load_model, pose_nms_options,  # noqa: E402
+                     setup_logging)
 
 
-def evaluate(model, loader, pck_thresholds, boxes="gt", oks=None):
+def evaluate(model, loader, pck_thresholds, boxes="gt", oks=None, pose_nms=None):
     """One pass over ``loader``.  ``pck_thresholds`` None skips ADE / PCK;
-    ``oks`` (an ``OksEvaluator``) is updated per batch, on the device.  Returns
-    (metrics, batches) or, with ``oks``, (metrics, batches, images)."""
+    ``oks`` (an ``OksEvaluator``) is updated per batch, on the device; with
+    ``pose_nms`` (``suppress_poses`` options) it scores the poses OKS pose-NMS
+    leaves, while the slot-wise ADE / PCK keep the unsuppressed outputs.
+    Returns (metrics, batches) or, with ``oks``, (metrics, batches, images)."""
     sums, n, images = defaultdict(float), 0, 0
     with torch.no_grad():
         for batch in loader:
@@ -56,7 +64,11 @@ def evaluate(model, loader, pck_thresholds, boxes="gt", oks=None):
                 for k, v in calculate_validation_metrics(out, batch, pck_thresholds).items():
                     sums[k] += v
             if oks is not None:
-                oks.update(out, batch)
+                if pose_nms is not None:
+                    out = suppress_poses(out, batch["orig_size"], **pose_nms)
+                    oks.update(out, batch, scores=out["pose_scores"])
+                else:
+                    oks.update(out, batch)
                 images += batch["image"].shape[0]
             n += 1
     metrics = {k: v / max(n, 1) for k, v in sums.items()}
@@ -79,10 +91,14 @@ def main(argv=None):
                     help="person boxes: the labels' (gt) or the model's person detector")
     ap.add_argument("--metric", default="pck", choices=["pck", "oks", "both"],
                     help="pck: slot-wise ADE / PCK; oks: COCO keypoint AP / AP50 / AP75 / AR; both")
+    add_pose_nms_arguments(ap)
     args = ap.parse_args(argv)
     if args.boxes == "detector" and args.metric != "oks":
         ap.error("ADE / PCK compare prediction slot p with ground-truth slot p and are not defined for detector "
                  "boxes, which have their own order and count: use --boxes detector --metric oks")
+    if args.pose_nms != "off" and args.metric == "pck":
+        ap.error("--pose-nms acts on the poses COCO OKS AP scores; ADE / PCK are slot-wise and ignore it: "
+                 "use --metric oks or --metric both")
     setup_logging()
     cfg = load_config(args.config)
     device = torch.device(args.device)
@@ -97,8 +113,11 @@ def main(argv=None):
         print(json.dumps({"split": args.split, "batches": n, **metrics}))
         return metrics
     metrics, n, images = evaluate(model, loader, thresholds if args.metric == "both" else None, boxes=args.boxes,
-                                  oks=OksEvaluator())
-    print(json.dumps({"split": args.split, "batches": n, "boxes": args.boxes, "images": images, **metrics}))
+                                  oks=OksEvaluator(), pose_nms=pose_nms_options(args))
+    line = {"split": args.split, "batches": n, "boxes": args.boxes, "images": images}
+    if args.pose_nms != "off":
+        line["pose_nms"] = args.pose_nms
+    print(json.dumps({**line, **metrics}))
     return metrics
 
 

@@ -28,7 +28,11 @@ Differences (documented in DESIGN.md):
     ``--output``: ``<stem>_keypoints<suffix>``, the overlay (boxes, skeleton,
     joints) drawn on the device at the image's own resolution
     (``dll.utils.draw_poses``, one call per forward), and
-    ``<stem>_keypoints.txt``, the prediction as YOLO-pose label lines.
+    ``<stem>_keypoints.txt``, the prediction as YOLO-pose label lines;
+  * ``--pose-nms hard|soft|soft-linear`` puts OKS pose-NMS
+    (``dll.utils.suppress_poses``, kpd_pose_nms) between the forward and the
+    outputs: of two boxes on one person only the higher-scoring pose is drawn,
+    written and counted.  ``off`` (the default) changes nothing.
 Runs on the HIP device (the accelerated path has no CPU fallback).
 """
 from __future__ import annotations
@@ -46,7 +50,7 @@ from dll.configs import (BackboneConfig, KeypointHeadConfig, ModelConfig,  # noq
                          PersonDetectionConfig, TrainingConfig)
 from dll.data import ITransform  # noqa: E402
 from dll.models import MultiPersonKeypointModel  # noqa: E402
-from dll.utils import draw_poses, format_pose_labels  # noqa: E402
+from dll.utils import draw_poses, format_pose_labels, suppress_poses  # noqa: E402
 
 KEYPOINT_NAMES = ["nose", "left_eye", "right_eye", "left_ear", "right_ear", "left_shoulder", "right_shoulder",
                   "left_elbow", "right_elbow", "left_wrist", "right_wrist", "left_hip", "right_hip", "left_knee",
@@ -82,6 +86,37 @@ def load_model(model_path, config_dict, device, precision="split"):
         own = model.state_dict()
         model.load_state_dict({k: v for k, v in sd.items() if k in own}, strict=False)
     return model.to(device).eval()
+
+
+POSE_NMS_CHOICES = ("off", "hard", "soft", "soft-linear")
+
+
+def add_pose_nms_arguments(ap):
+    """--pose-nms / --pose-nms-threshold / --pose-nms-vis, shared with evaluate.py."""
+    ap.add_argument("--pose-nms", default="off", choices=POSE_NMS_CHOICES,
+                    help="OKS pose-NMS between pose scoring and the output (dll.utils.suppress_poses): hard "
+                         "suppression, or soft score decay (Gaussian / linear)")
+    ap.add_argument("--pose-nms-threshold", type=float, default=0.9, help="OKS threshold of --pose-nms")
+    ap.add_argument("--pose-nms-vis", type=float, default=0.2,
+                    help="keypoints whose heatmap peak is not above this in both poses do not count in the pose OKS")
+
+
+def pose_nms_options(args):
+    """``suppress_poses`` options of the parsed flags, None with --pose-nms off."""
+    if args.pose_nms == "off":
+        return None
+    return {"mode": args.pose_nms.replace("-", "_"), "threshold": args.pose_nms_threshold,
+            "vis_threshold": args.pose_nms_vis}
+
+
+def _suppress(outputs, images, pose_nms):
+    """``outputs`` after OKS pose-NMS at the decoded ``images``' own (W, H);
+    unchanged without options, and when no forward ran: the all-zero [B, 1, K, 2]
+    keypoints of a call without any box (``bboxes=None``, an empty label file)
+    hold no pose to suppress."""
+    if pose_nms is None or outputs["keypoints"].dim() != 5:
+        return outputs
+    return suppress_poses(outputs, [im.size for im in images], **pose_nms)
 
 
 def make_transform(in_channels: int, size, device):
@@ -122,12 +157,14 @@ def save_prediction(drawn, outputs, output_path):
 
 
 def predict_single_image(model, image_path, transform, device, gt_path=None, output_path=None,
-                         reference_zeros=False, return_outputs=False):
+                         reference_zeros=False, return_outputs=False, pose_nms=None):
     """Reference predict_single_image (:64-131).  Without a GT file the
     detector branch runs (``model({'image': x})``: no 'bboxes' key), unless
     ``reference_zeros`` asks for the reference's ``bboxes=None`` call.  With
-    ``output_path`` the overlay (drawn on the device, ``dll.utils.draw_poses``)
-    and the label file are written (``save_prediction``)."""
+    ``pose_nms`` (``suppress_poses`` options) the outputs go through OKS
+    pose-NMS before anything is drawn, saved or logged.  With ``output_path``
+    the overlay (drawn on the device, ``dll.utils.draw_poses``) and the label
+    file are written (``save_prediction``)."""
     from PIL import Image
     image = Image.open(image_path).convert("RGB")
     x = transform(image).unsqueeze(0).to(device)
@@ -140,7 +177,7 @@ def predict_single_image(model, image_path, transform, device, gt_path=None, out
         batch, mode = {"image": x}, "person detector"
     logging.info(f"{Path(image_path).name}: boxes from {mode}")
     with torch.no_grad():
-        outputs = model(batch)
+        outputs = _suppress(model(batch), [image], pose_nms)
     if output_path is not None:
         save_prediction(draw_poses([image], outputs)[0], outputs, output_path)
     if bboxes is None and not reference_zeros:
@@ -192,6 +229,14 @@ def _slice_outputs(outputs, i, persons=None):
 
 def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir=None, reference_zeros=False,
                       batch_size=64):
+    """``predict_directory_nms`` without OKS pose-NMS: the reference's
+    predict_directory (:133-160) and its arguments."""
+    return predict_directory_nms(model, input_dir, transform, device, output_dir, gt_dir=gt_dir,
+                                 reference_zeros=reference_zeros, batch_size=batch_size)
+
+
+def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt_dir=None, reference_zeros=False,
+                          batch_size=64, pose_nms=None):
     """Reference predict_directory (:133-160) as a batched device pipeline:
     the images with the reference's extensions, in sorted order, are decoded
     on the host; every chunk of at most ``batch_size`` is preprocessed by one
@@ -201,7 +246,9 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
     all-zero boxes); the others form the person-detector batch, or the
     ``bboxes=None`` batch with ``reference_zeros``.  Each image logs its mode
     and prints the block of ``predict_single_image``.  A file that fails to
-    decode is logged and skipped, as in the reference's try/except.  With an
+    decode is logged and skipped, as in the reference's try/except.  With
+    ``pose_nms`` (``suppress_poses`` options) every forward's outputs go
+    through OKS pose-NMS at its images' own sizes first.  With an
     ``output_dir`` every forward's batched outputs are drawn onto its images by
     one ``draw_poses`` call and each image's overlay and label file are written
     (``save_prediction``).  Returns
@@ -244,6 +291,7 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
                 for j, i in enumerate(given):
                     bt[j, :persons[j]] = decoded[i][2]
                 out = model({"image": x[given] if other else x, "bboxes": bt})
+                out = _suppress(out, [decoded[i][1] for i in given], pose_nms)
                 draw(given, out)
                 for j, i in enumerate(given):
                     per_image[i] = ("given boxes", _slice_outputs(out, j, persons[j]))
@@ -253,6 +301,7 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
                     out, mode = model({"image": xo, "bboxes": None}), "reference zeros (bboxes=None)"
                 else:
                     out, mode = model({"image": xo}), "person detector"
+                out = _suppress(out, [decoded[i][1] for i in other], pose_nms)
                 draw(other, out)
                 for j, i in enumerate(other):
                     per_image[i] = (mode, _slice_outputs(out, j))
@@ -286,6 +335,7 @@ def main(argv=None):
                     help="without --gt, call the model with bboxes=None like the reference (all-zero keypoints) "
                          "instead of running the person detector")
     ap.add_argument("--size", default=None, help="HxW input size (default: input_size square)")
+    add_pose_nms_arguments(ap)
     args = ap.parse_args(argv)
     setup_logging()
     cfg = load_config(args.config)
@@ -304,11 +354,11 @@ def main(argv=None):
         output_path = output_path_for(args.output, inp)
         results.append((inp, predict_single_image(model, inp, transform, device, gt if gt and gt.is_file() else None,
                                                   output_path=output_path, reference_zeros=args.reference_zeros,
-                                                  return_outputs=True)[1]))
+                                                  return_outputs=True, pose_nms=pose_nms_options(args))[1]))
         logging.info(f"Saved visualization to {output_path}")
     else:
-        results = predict_directory(model, inp, transform, device, args.output, gt_dir=gt,
-                                    reference_zeros=args.reference_zeros)
+        results = predict_directory_nms(model, inp, transform, device, args.output, gt_dir=gt,
+                                        reference_zeros=args.reference_zeros, pose_nms=pose_nms_options(args))
     logging.info("Prediction completed successfully!")
     return {"model": model, "results": results}
 
