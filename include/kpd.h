@@ -385,6 +385,44 @@ int kpd_pose_nms(const float* kpts, const float* scores, const float* area, cons
                  float min_score, int max_keep, double* oks, int32_t* keep, int32_t* n_keep, float* scores_out,
                  int32_t* suppressed_by, void* stream);
 
+/* Flip-test merge: the heatmaps of a forward over the images
+ * and of one over their left-right mirrors, averaged and decoded in one launch.
+ *   heat_a, heat_b  [n][P][K][H][W] fp32 (device): kpd_forward's heatmap of the
+ *                   straight and of the mirrored pass, in the forward's
+ *                   compacted person-slot order;
+ *   boxes           [n][P][4] fp32 cxcywh (device): the STRAIGHT pass's boxes in
+ *                   caller order, zero rows included.  The compaction is derived
+ *                   here by the forward's rule: a box whose four values are all
+ *                   == 0 is skipped, slot s of an image is its s-th other box;
+ *   pairs           [K] (host; read before the call returns): the joint whose
+ *                   mirrored plane merges into joint k -- an involution
+ *                   (0 <= pairs[k] < K, pairs[pairs[k]] == k).
+ * Live slot (s < the image's non-zero boxes), j = pairs[k]:
+ *   m[k][y][x] = 0.5f * (a[k][y][x] + b[j][y][W-1-x])   (one fp32 add, an exact
+ *   halving); peak = max m; the keypoint is the forward's decode of m with the
+ *   slot's box: soft-argmax E[x] / (W-1), E[y] / (H-1) under softmax(m) (0 for
+ *   W == 1 / H == 1), x = clamp(kx * w + (cx - w / 2), 0, 1), y alike; the
+ *   visibility is one-hot of sigmoid(peak) (fp32, compared as a double) < 0.3 /
+ *   < 0.7 / else.
+ * Padding slot: zero keypoints, visibilities, peak and heat_out plane; the dummy
+ * person (slot 0 of an image without a non-zero box) has visibility class 0 set
+ * -- the values kpd_forward writes.
+ * Outputs (device): heat_out [n][P][K][H][W] (may be NULL; may equal heat_a:
+ * merged in place; any other overlap with heat_a or heat_b is KPD_EINVAL),
+ * keypoints [n][P][K][2] (the memory of the forward's [n][P][1][K][2]),
+ * visibilities [n][P][K][3], peaks [n][P][K] (may be NULL).
+ * One launch, one wave per (slot, keypoint) plane, each input plane read once;
+ * an image's result does not depend on the others of the call.  Arguments are
+ * checked before any device work (KPD_EINVAL, the message names the argument):
+ * K in [1, KPD_FLIP_MAX_K], H, W in [1, KPD_FLIP_MAX_SIDE], P >= 1; n = 0
+ * returns KPD_OK without a launch.  No synchronisation, no allocation.
+ * tests/flip_ref.py restates the rules in numpy. */
+#define KPD_FLIP_MAX_K 32
+#define KPD_FLIP_MAX_SIDE 1024
+int kpd_flip_merge(const float* heat_a, const float* heat_b, const float* boxes, const int32_t* pairs, int n, int P,
+                   int K, int H, int W, float* heat_out, float* keypoints, float* visibilities, float* peaks,
+                   void* stream);
+
 /* Training loss: AdaptiveHeatmapLoss.forward
  * (dll/losses/keypoint_loss.py:202-280).  pred, gt: [B][K][H][W] fp32,
  * target_weight: [B][K] or NULL (all device).  Threshold = clamp(torch.quantile(

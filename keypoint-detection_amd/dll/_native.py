@@ -34,7 +34,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
-           "kpd_oks_match", "kpd_pose_nms")
+           "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -53,6 +53,9 @@ OKS_MAX_G = 64         # KPD_OKS_MAX_G: ground-truth slots per image
 POSE_NMS_MAX_D = 64    # KPD_POSE_NMS_MAX_D: pose slots per image, one lane each
 POSE_NMS_MAX_K = 32    # KPD_POSE_NMS_MAX_K: keypoints per pose
 POSE_NMS_HARD, POSE_NMS_SOFT, POSE_NMS_SOFT_LINEAR = 0, 1, 2
+# kpd_flip_merge (include/kpd.h): limits of one call
+FLIP_MAX_K = 32        # KPD_FLIP_MAX_K: keypoints per pose
+FLIP_MAX_SIDE = 1024   # KPD_FLIP_MAX_SIDE: heatmap height / width
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
@@ -122,6 +125,7 @@ def load() -> ctypes.CDLL:
         [c_void_p] * 8
     lib.kpd_pose_nms.argtypes = [c_void_p] * 5 + [ctypes.POINTER(ctypes.c_float)] + [c_int] * 4 + \
         [ctypes.c_float] * 3 + [c_int] + [c_void_p] * 6
+    lib.kpd_flip_merge.argtypes = [c_void_p] * 3 + [ctypes.POINTER(ctypes.c_int32)] + [c_int] * 5 + [c_void_p] * 5
     lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float
@@ -388,6 +392,45 @@ def decode_heatmaps(heat: torch.Tensor, mode: int, param: float = 0.0):
         check(lib.kpd_decode_heatmaps(_ptr(heat), B * K, H, W, int(mode), float(param), _ptr(kp), _ptr(sc), _ptr(vis),
                                       _stream(heat.device)), "kpd_decode_heatmaps")
     return kp, sc, vis
+
+
+def flip_merge(heat_a: torch.Tensor, heat_b: torch.Tensor, boxes: torch.Tensor, pairs, heat_out, keypoints,
+               visibilities, peaks) -> None:
+    """``kpd_flip_merge`` (include/kpd.h) on contiguous fp32 device tensors:
+    heat_a, heat_b [n,P,K,H,W], boxes [n,P,4], ``pairs`` K ints (host);
+    writes keypoints (n*P*K*2 values), visibilities (n*P*K*3) and the nullable
+    heat_out [n,P,K,H,W] (may be heat_a itself) and peaks (n*P*K).  The call
+    does not synchronise."""
+    named = (("heat_a", heat_a), ("heat_b", heat_b), ("boxes", boxes), ("heat_out", heat_out),
+             ("keypoints", keypoints), ("visibilities", visibilities), ("keypoint_peaks", peaks))
+    if not isinstance(heat_a, torch.Tensor):
+        raise TypeError("heat_a must be a tensor")
+    if heat_a.dim() != 5:
+        raise ValueError(f"heat_a must be [n, P, K, H, W], got {list(heat_a.shape)}")
+    n, P, K, H, W = heat_a.shape
+    numel = {"heat_a": n * P * K * H * W, "heat_b": n * P * K * H * W, "boxes": n * P * 4,
+             "heat_out": n * P * K * H * W, "keypoints": n * P * K * 2, "visibilities": n * P * K * 3,
+             "keypoint_peaks": n * P * K}
+    for name, t in named:
+        if t is None and name in ("heat_out", "keypoint_peaks"):
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor")
+        _require_cuda(t, name)
+        if t.device != heat_a.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {heat_a.device}")
+        if t.numel() != numel[name]:
+            raise ValueError(f"{name} has {t.numel()} values, heat_a {list(heat_a.shape)} needs {numel[name]}")
+    if tuple(heat_b.shape) != tuple(heat_a.shape):
+        raise ValueError(f"heat_b {list(heat_b.shape)} does not match heat_a {list(heat_a.shape)}")
+    pr = [int(v) for v in pairs]
+    if len(pr) != K:
+        raise ValueError(f"{len(pr)} flip pairs for {K} keypoints")
+    with torch.cuda.device(heat_a.device):
+        rc = load().kpd_flip_merge(_ptr(heat_a), _ptr(heat_b), _ptr(boxes), (ctypes.c_int32 * max(K, 1))(*pr),
+                                   n, P, K, H, W, _ptr(heat_out), _ptr(keypoints), _ptr(visibilities), _ptr(peaks),
+                                   _stream(heat_a.device))
+    check(rc, "kpd_flip_merge")
 
 
 def roi_align(features: torch.Tensor, rois: torch.Tensor, output_size, spatial_scale: float = 1.0,

@@ -123,10 +123,28 @@ class MultiPersonKeypointModel(nn.Module):
     path stores FPN level 0 only where the ROI aligns read it; True stores
     the whole map (for inspecting ``native_plan(dev).debug_buffer("feat0")``).
     Outputs are identical either way.
+
+    ``flip_test`` (keyword and settable attribute, default False): every
+    forward also runs the left-right mirrored images with the mirrored boxes
+    (``dll.utils.flip``), and ``kpd_flip_merge`` averages the two heatmaps --
+    the mirrored pass mirrored back, its left / right joint planes swapped --
+    and decodes the average: ``heatmap``, ``keypoints`` and ``visibilities``
+    are the merged ones and ``keypoint_peaks`` [B, P, K] (the merged planes'
+    maxima) is added.  With caller boxes both passes run as one forward over
+    the concatenated batch (the same values as two forwards, bit for bit in
+    split / fp32 precision; the merged heatmap is then a view of the first
+    half of that forward's output).  In the detector branch the straight pass
+    detects and a second forward takes its mirrored boxes as caller boxes;
+    ``boxes`` and ``box_scores`` are the straight pass's.  The dual head's
+    ``kh_*`` outputs
+    stay the straight pass's (KEYPOINT_HEAD regresses coordinates: there is
+    no heatmap to merge).  A batch with targets has its loss computed on the
+    merged outputs.  The one-pixel misalignment of mirrored strided features
+    is not compensated.  Off, every output is unchanged.
     """
 
     def __init__(self, config: ModelConfig, training_config: TrainingConfig, precision: str = "split",
-                 dual_head: bool = False, max_persons: int = 5, streams: int = 1):
+                 dual_head: bool = False, max_persons: int = 5, streams: int = 1, flip_test: bool = False):
         super().__init__()
         if precision not in _native.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_native.PRECISIONS)}")
@@ -147,6 +165,7 @@ class MultiPersonKeypointModel(nn.Module):
         self.precision = precision      # (property: also sets the submodules' own plans' precision)
         self.streams = streams          # sub-batch streams for B >= 32 (kpd_plan_set_streams)
         self.full_level0 = False        # store all of FPN level 0 (debug copy), not just the ROI footprints
+        self.flip_test = bool(flip_test)   # merge a mirrored pass into heatmap / keypoints / visibilities
         self._plan: Optional[_native.Plan] = None
         self._plan_key = None
         self._plan_streams: Optional[int] = None
@@ -287,6 +306,8 @@ class MultiPersonKeypointModel(nn.Module):
             bt = torch.zeros(B, P, 4, device=dev)
             scores = torch.zeros(B, P, device=dev)
             out = self._run(plan, image, bt, B, P, flags | _native.FLAG_DETECT, scores)
+            if self.flip_test:
+                self._merge_mirrored(plan, image, bt, B, P, flags, out)
             out["boxes"] = [bt[i] for i in range(B)]
             out["box_scores"] = scores
             return out
@@ -310,9 +331,44 @@ class MultiPersonKeypointModel(nn.Module):
             bt = torch.stack([b.to(dev, torch.float32) for b in boxes]).contiguous()   # [nb,P,4]
         if bt.dim() != 3 or bt.size(-1) != 4:
             raise ValueError(f"Invalid bboxes format: {tuple(bt.shape)}")
-        out = self._run(plan, image, bt, nb, P, flags)
+        if self.flip_test and nb == B:
+            out = self._run_both(plan, image, bt, nb, P, flags)
+        else:
+            out = self._run(plan, image, bt, nb, P, flags)
+            if self.flip_test:
+                self._merge_mirrored(plan, image, bt, nb, P, flags, out)
         out["boxes"] = boxes
         return out
+
+    def _run_both(self, plan, image, bt, nb, P, flags) -> Dict[str, torch.Tensor]:
+        """Flip-test with caller boxes: ONE forward over the straight and the
+        mirrored images (boxes alike), then the merge of its two halves.  An
+        image's result does not depend on its batch (split / fp32), so this
+        equals two forwards bit for bit; it is measured faster (DESIGN.md §7
+        Round 12: a small batch is bound by the forward's launches, which it
+        pays once).  The merged heatmap is a view of the first half, and so are
+        the dual head's outputs, which stay the straight pass's."""
+        from ..utils.flip import flip_merge, mirror_boxes, mirror_images
+        both = self._run(plan, torch.cat([image, mirror_images(image)]), torch.cat([bt, mirror_boxes(bt)]), 2 * nb, P,
+                         flags)
+        out = flip_merge(both["heatmap"][:nb], both["heatmap"][nb:], bt, inplace=True)
+        for k in ("kh_keypoints", "kh_visibilities"):
+            if k in both:
+                out[k] = both[k][:nb]
+        return out
+
+    def _merge_mirrored(self, plan, image, bt, nb, P, flags, out) -> None:
+        """Flip-test as a second forward: the mirrored pass over
+        ``mirror_boxes(bt)`` as caller boxes and the merge, in place of
+        ``out``'s heatmap / keypoints / visibilities.  The detector branch
+        needs it (``bt``: the boxes the straight pass detected), and so do
+        boxes for fewer images than the batch holds.  The mirrored pass runs
+        with the straight pass's flags, the dual head included (its outputs are
+        dropped): the flags select kernels, and both passes must take the same
+        ones for the merge to be mirror-equivariant bit for bit."""
+        from ..utils.flip import flip_merge, mirror_boxes, mirror_images
+        mirrored = self._run(plan, mirror_images(image), mirror_boxes(bt).contiguous(), nb, P, flags)
+        out.update(flip_merge(out["heatmap"], mirrored["heatmap"], bt, inplace=True))
 
     def _run(self, plan, image, bt, nb, P, flags, box_scores=None) -> Dict[str, torch.Tensor]:
         dev, K = image.device, self.num_keypoints

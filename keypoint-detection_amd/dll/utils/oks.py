@@ -100,9 +100,14 @@ def oks_match(pred_kpts: torch.Tensor, pred_scores: torch.Tensor, gt_kpts: torch
 
 def keypoint_peaks(outputs: Dict) -> torch.Tensor:
     """The maximum of every heatmap plane of a forward's ``outputs``, [B, P, K]:
-    one confidence per keypoint (``outputs['heatmap']`` is a sigmoid)."""
+    one confidence per keypoint (``outputs['heatmap']`` is a sigmoid).  Outputs
+    that carry ``keypoint_peaks`` (a flip-test forward: ``kpd_flip_merge``
+    writes them with the merged map) return that tensor -- the same values
+    with one pass over the heatmap fewer."""
     k = torch.as_tensor(outputs["keypoints"])
     B, dev = k.shape[0], k.device
+    if outputs.get("keypoint_peaks") is not None:
+        return torch.as_tensor(outputs["keypoint_peaks"]).to(dev, torch.float32)
     P = keypoints_tensor(outputs, B).shape[1]
     heat = outputs.get("heatmap")
     if heat is None:

@@ -20,6 +20,12 @@ OKS pose-NMS (kpd_pose_nms, ``dll.utils.suppress_poses``) between the forward
 and the OKS matching: two boxes on one person no longer count as a true and a
 false positive.  ADE / PCK are slot-wise and keep the unsuppressed outputs.
 
+``--flip-test`` turns on the model's flip-test (``model.flip_test``: a second
+forward over the mirrored images, the two heatmaps merged and decoded by
+kpd_flip_merge), the protocol top-down pose results are usually reported with:
+every metric is then computed on the merged outputs and the JSON line carries
+``"flip_test": true``.  Without the option the line has no such key.
+
 The loader's ``efficient_collate_fn`` drops images without a labelled person
 from a batch, so detections on such images are not counted as false
 positives (inherited behaviour).
@@ -43,8 +49,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from dll.data import create_optimized_dataloader  # noqa: E402
 from dll.utils import OksEvaluator, calculate_validation_metrics, suppress_poses  # noqa: E402
-from predict import (add_pose_nms_arguments, load_config, load_model, pose_nms_options,  # noqa: E402
-                     setup_logging)
+from predict import (add_flip_test_argument, add_pose_nms_arguments, flip_test_enabled, load_config,  # noqa: E402
+                     load_model, pose_nms_options, setup_logging)
 
 
 def evaluate(model, loader, pck_thresholds, boxes="gt", oks=None, pose_nms=None):
@@ -92,6 +98,7 @@ def main(argv=None):
     ap.add_argument("--metric", default="pck", choices=["pck", "oks", "both"],
                     help="pck: slot-wise ADE / PCK; oks: COCO keypoint AP / AP50 / AP75 / AR; both")
     add_pose_nms_arguments(ap)
+    add_flip_test_argument(ap)
     args = ap.parse_args(argv)
     if args.boxes == "detector" and args.metric != "oks":
         ap.error("ADE / PCK compare prediction slot p with ground-truth slot p and are not defined for detector "
@@ -108,16 +115,19 @@ def main(argv=None):
                                          img_size=bcfg["input_size"], grayscale=bcfg.get("in_channels", 3) == 1,
                                          device=device)
     model = load_model(args.model, cfg, device, args.precision)
+    flip = {"flip_test": True} if flip_test_enabled(args) else {}   # the key appears only with the option on
+    if flip:
+        model.flip_test = True
     if args.metric == "pck":
         metrics, n = evaluate(model, loader, thresholds)
-        print(json.dumps({"split": args.split, "batches": n, **metrics}))
+        print(json.dumps({"split": args.split, "batches": n, **flip, **metrics}))
         return metrics
     metrics, n, images = evaluate(model, loader, thresholds if args.metric == "both" else None, boxes=args.boxes,
                                   oks=OksEvaluator(), pose_nms=pose_nms_options(args))
     line = {"split": args.split, "batches": n, "boxes": args.boxes, "images": images}
     if args.pose_nms != "off":
         line["pose_nms"] = args.pose_nms
-    print(json.dumps({**line, **metrics}))
+    print(json.dumps({**line, **flip, **metrics}))
     return metrics
 
 

@@ -32,7 +32,11 @@ Differences (documented in DESIGN.md):
   * ``--pose-nms hard|soft|soft-linear`` puts OKS pose-NMS
     (``dll.utils.suppress_poses``, kpd_pose_nms) between the forward and the
     outputs: of two boxes on one person only the higher-scoring pose is drawn,
-    written and counted.  ``off`` (the default) changes nothing.
+    written and counted.  ``off`` (the default) changes nothing;
+  * ``--flip-test`` turns on the model's flip-test (a second forward over the
+    mirrored image, the two heatmaps merged and decoded by kpd_flip_merge):
+    overlays, label files and the printout come from the merged outputs.
+    Without the option nothing changes.
 Runs on the HIP device (the accelerated path has no CPU fallback).
 """
 from __future__ import annotations
@@ -99,6 +103,17 @@ def add_pose_nms_arguments(ap):
     ap.add_argument("--pose-nms-threshold", type=float, default=0.9, help="OKS threshold of --pose-nms")
     ap.add_argument("--pose-nms-vis", type=float, default=0.2,
                     help="keypoints whose heatmap peak is not above this in both poses do not count in the pose OKS")
+
+
+def add_flip_test_argument(ap):
+    """--flip-test [on|off], shared with evaluate.py: the bare option means on, the default is off."""
+    ap.add_argument("--flip-test", nargs="?", const="on", default="off", choices=("on", "off"),
+                    help="also run every image's left-right mirror and decode the average of the two heatmaps "
+                         "(MultiPersonKeypointModel.flip_test, kpd_flip_merge); costs a second forward")
+
+
+def flip_test_enabled(args) -> bool:
+    return args.flip_test == "on"
 
 
 def pose_nms_options(args):
@@ -336,6 +351,7 @@ def main(argv=None):
                          "instead of running the person detector")
     ap.add_argument("--size", default=None, help="HxW input size (default: input_size square)")
     add_pose_nms_arguments(ap)
+    add_flip_test_argument(ap)
     args = ap.parse_args(argv)
     setup_logging()
     cfg = load_config(args.config)
@@ -345,6 +361,9 @@ def main(argv=None):
     transform = make_transform(bcfg.get("in_channels", 3), size, device)
     logging.info(f"Loading model from {args.model}")
     model = load_model(args.model, cfg, device, args.precision)
+    if flip_test_enabled(args):
+        model.flip_test = True
+        logging.info("flip-test on: every forward also runs the mirrored image and decodes the merged heatmaps")
     inp = Path(args.input)
     gt = Path(args.gt) if args.gt else None
     Path(args.output).mkdir(parents=True, exist_ok=True)
