@@ -423,6 +423,82 @@ int kpd_flip_merge(const float* heat_a, const float* heat_b, const float* boxes,
                    int K, int H, int W, float* heat_out, float* keypoints, float* visibilities, float* peaks,
                    void* stream);
 
+/* Training augmentation: n uint8 HWC images warped by a
+ * per-image affine map (mirror, rotation, zoom) with optional gain / offset,
+ * and the labels moved with the pixels.  What the reference's
+ * AugmentationConfig (flip, rotate.max_angle, scale.range, prob) promises and
+ * its KeypointAugmentation.__call__ leaves as a stub.
+ *   srcs / heights / widths / pitches: host arrays of n entries -- device
+ *       pointers to source images of `channels` (1 or 3) channels, each with
+ *       its own size (sides in [1, KPD_AUG_MAX_SIDE]) and row pitch in bytes
+ *       (any pitch >= width * channels);
+ *   dsts: host array of n device pointers; destination i is dense
+ *       [height_i][width_i][channels].  No destination may overlap any source
+ *       (the warp is a gather).
+ *   Per image (host arrays): q [n][6] int32, the INVERSE map in Q16 in
+ *       pixel-index coordinates, rows (q00 q01 q02), (q10 q11 q12), with
+ *       |q00|, |q01|, |q10|, |q11| < 2^19; N [n][6] double, the FORWARD map in
+ *       normalised coordinates; mirror [n] (non-zero: left / right joints
+ *       swap); gain [n] in [0, 65535] and offset [n], |offset| < 2^24, in Q8
+ *       (identity 256 and 0).
+ *   Per call (host): fill [3] uint8, the colour of a tap outside the source;
+ *       pairs [K], the joint a mirror exchanges joint k with -- an involution,
+ *       as for kpd_flip_merge.
+ *   Labels (device, fp32): keypoints [n][P][K][2] normalised (x, y),
+ *       visibilities [n][P][K], boxes [n][P][4] cxcywh, and one output buffer
+ *       of the same shape for each.  All three inputs may be NULL for an
+ *       image-only call; P, K, pairs and the outputs are then ignored.  No
+ *       label output may overlap a label input (the mirror swaps joints).
+ * Image rule, for output pixel (x, y) and channel ch; exact integer
+ * arithmetic, arithmetic shifts, t(yy, xx) = src[yy][xx][ch] inside the source
+ * and fill[ch] outside:
+ *   sx  = q00 * x + q01 * y + q02            (64-bit; sy with row 1)
+ *   sx5 = (sx + 1024) >> 11                  (1/32-pixel units)
+ *   ix  = sx5 >> 5,  fx = sx5 & 31           (iy, fy alike)
+ *   acc = (32-fx)*(32-fy)*t(iy,ix) + fx*(32-fy)*t(iy,ix+1) + (32-fx)*fy*t(iy+1,ix) + fx*fy*t(iy+1,ix+1)
+ *   v   = (acc + 512) >> 10
+ *   out = clamp((v * gain + offset + 128) >> 8, 0, 255)
+ * Label rule, float64 with every operation rounded on its own, results stored
+ * as fp32.  Output joint k is computed from input joint s = pairs[k] with the
+ * mirror flag, s = k without, coordinates and visibility both.  A source joint
+ * with v == 0 or x == 0 and y == 0 (padding, an unlabelled COCO joint) is
+ * copied unchanged.  Any other maps to x' = (N00 * x + N01 * y) + N02, y'
+ * alike; when the fp32 (x', y') is not in [0, 1) x [0, 1) the joint left the
+ * frame: v' = 0, (x', y') = (0, 0); else v' = v.  An all-zero box stays
+ * all-zero; any other has its corners cx -+ 0.5 * w, cy -+ 0.5 * h mapped
+ * through N, the axis-aligned hull taken and each side clipped to [0, 1]; the
+ * row is (0.5 * (x0 + x1), 0.5 * (y0 + y1), x1 - x0, y1 - y0), or all-zero when
+ * the clipped width or height is <= 0 (the person left the frame; the forward
+ * skips zero boxes).  A person's joints follow the joint rule whatever became
+ * of its box.
+ *
+ * One launch per chunk of KPD_AUG_CHUNK images: one 256-thread workgroup per
+ * KPD_AUG_TILE_W x KPD_AUG_TILE_H output tile, four consecutive pixels per
+ * thread, over a flattened tile list of the chunk's images; the label work
+ * rides in the same launch as extra workgroups behind the tiles.  Images and
+ * parameters are addressed through a descriptor table passed by value.  Image
+ * i's result does not depend on the other images of the call.
+ *
+ * Arguments are checked before any device work; a failure is KPD_EINVAL with
+ * the argument named and per-image failures read "image <i>: ...": n >= 0,
+ * channels in {1, 3}, the limits above, K in [1, KPD_AUG_MAX_K], P >= 1 (with
+ * labels), pairs an involution, non-null arrays, the two overlap rules.  n = 0
+ * returns KPD_OK without a launch.  No synchronisation, no allocation; no host
+ * array is read after the call returns.  tests/augment_ref.py restates the
+ * rules in numpy: images bit-equal, labels equal but for the fp32 store.
+ * Parity with OpenCV's warpAffine (whose 1/32-pixel grid this follows) is
+ * unpinned. */
+#define KPD_AUG_CHUNK 16       /* images per descriptor table */
+#define KPD_AUG_TILE_W 64      /* pixels of one workgroup's tile */
+#define KPD_AUG_TILE_H 16
+#define KPD_AUG_MAX_SIDE 16384
+#define KPD_AUG_MAX_K 32
+int kpd_augment_batch(const uint8_t* const* srcs, const int* heights, const int* widths, const int* pitches,
+                      uint8_t* const* dsts, int n, int channels, const int32_t* q, const double* N,
+                      const int* mirror, const int32_t* gain, const int32_t* offset, const uint8_t* fill,
+                      const int32_t* pairs, const float* keypoints, const float* visibilities, const float* boxes,
+                      int P, int K, float* keypoints_out, float* visibilities_out, float* boxes_out, void* stream);
+
 /* Training loss: AdaptiveHeatmapLoss.forward
  * (dll/losses/keypoint_loss.py:202-280).  pred, gt: [B][K][H][W] fp32,
  * target_weight: [B][K] or NULL (all device).  Threshold = clamp(torch.quantile(

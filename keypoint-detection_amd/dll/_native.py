@@ -34,7 +34,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
-           "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge")
+           "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -56,6 +56,12 @@ POSE_NMS_HARD, POSE_NMS_SOFT, POSE_NMS_SOFT_LINEAR = 0, 1, 2
 # kpd_flip_merge (include/kpd.h): limits of one call
 FLIP_MAX_K = 32        # KPD_FLIP_MAX_K: keypoints per pose
 FLIP_MAX_SIDE = 1024   # KPD_FLIP_MAX_SIDE: heatmap height / width
+# kpd_augment_batch (include/kpd.h): images per descriptor table, one workgroup's tile, limits
+AUG_CHUNK = 16         # KPD_AUG_CHUNK
+AUG_TILE_W = 64        # KPD_AUG_TILE_W
+AUG_TILE_H = 16        # KPD_AUG_TILE_H
+AUG_MAX_SIDE = 16384   # KPD_AUG_MAX_SIDE
+AUG_MAX_K = 32         # KPD_AUG_MAX_K: keypoints per pose
 FLAG_DETECT = 1
 FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
@@ -126,6 +132,10 @@ def load() -> ctypes.CDLL:
     lib.kpd_pose_nms.argtypes = [c_void_p] * 5 + [ctypes.POINTER(ctypes.c_float)] + [c_int] * 4 + \
         [ctypes.c_float] * 3 + [c_int] + [c_void_p] * 6
     lib.kpd_flip_merge.argtypes = [c_void_p] * 3 + [ctypes.POINTER(ctypes.c_int32)] + [c_int] * 5 + [c_void_p] * 5
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    lib.kpd_augment_batch.argtypes = [ctypes.POINTER(c_void_p)] + [ctypes.POINTER(c_int)] * 3 + \
+        [ctypes.POINTER(c_void_p), c_int, c_int, i32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int),
+         i32p, i32p, u8p, i32p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kpd_fpn0x_class_table.argtypes = [ctypes.POINTER(c_int)] * 4
     lib.kpd_nms.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_void_p]
     c_float = ctypes.c_float

@@ -1,9 +1,10 @@
 """Training configuration.  Only ``pck_thresholds`` is read on the inference
-hot path; the remaining fields are kept so the reference's constructor call
-``TrainingConfig()`` and YAML dicts keep working (reference:
-dll/configs/training_config.py:94-133).  Training itself is out of scope."""
+hot path and ``augmentation`` by the device augmentation
+(``dll.data.KeypointAugmentation``); the remaining fields are kept so the
+reference's constructor call ``TrainingConfig()`` and YAML dicts keep working
+(reference: dll/configs/training_config.py:94-133).  No trainer exists."""
 from dataclasses import dataclass, field
-from typing import List
+from typing import Any, Dict, List, Union
 
 from .base_config import BaseConfig, DeviceConfig
 
@@ -20,8 +21,23 @@ class OptimizerConfig(BaseConfig):
 
 @dataclass
 class AugmentationConfig(BaseConfig):
+    """The reference's fields (its YAML block constructs this class), plus
+    ``color`` and ``fill``.  Each enabled transform is applied on its own with
+    probability ``prob`` (``KeypointAugmentation.sample``)."""
     enabled: bool = False
     prob: float = 0.5
+    flip: Dict[str, bool] = field(default_factory=lambda: {"enabled": True, "horizontal": True})
+    rotate: Dict[str, Union[bool, float]] = field(default_factory=lambda: {"enabled": True, "max_angle": 30.0})
+    scale: Dict[str, Any] = field(default_factory=lambda: {"enabled": True, "range": [0.8, 1.2]})
+    color: Dict[str, Union[bool, float]] = field(
+        default_factory=lambda: {"enabled": False, "brightness": 0.2, "contrast": 0.2})
+    fill: Any = 0   # colour of a tap outside the source image: one value or three
+
+    def validate(self) -> None:
+        assert 0 <= self.prob <= 1, "prob must be between 0 and 1"
+        assert float(self.rotate.get("max_angle", 0.0)) >= 0, "rotate.max_angle must not be negative"
+        lo, hi = self.scale.get("range", [1.0, 1.0])
+        assert 0 < lo <= hi, "scale.range must satisfy 0 < range[0] <= range[1]"
 
 
 @dataclass

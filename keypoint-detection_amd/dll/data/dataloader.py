@@ -4,7 +4,8 @@
 What runs where:
 
 * host: directory scan, image decode (Pillow), label text parsing (numpy);
-* device: ``ITransform`` (``kpd_preprocess``) and the target heatmaps
+* device: the training augmentation (``kpd_augment_batch``, train split only),
+  ``ITransform`` (``kpd_preprocess``) and the target heatmaps
   (``kpd_target_heatmaps``), so a sample's ``image`` and ``heatmaps`` are
   already resident on the GPU;
 * collate: padding copies into device tensors (plumbing).
@@ -27,7 +28,9 @@ Differences: images are decoded by Pillow, not ``cv2.imread`` (the JPEG
 decoders may differ by a grey level; cv2 is absent here), and DataLoader
 workers are not used when the dataset runs on a GPU (forked workers cannot
 share the HIP context) -- the GPU stages are fast enough not to need them.
-Training augmentation (``KeypointAugmentation``) is out of scope.
+Training augmentation (``KeypointAugmentation``, augmentation.py) runs on the
+device for the train split, in the reference's order: filter, truncate,
+augment, transform, targets.  The reference's own augmentation is a stub.
 """
 from __future__ import annotations
 
@@ -121,9 +124,7 @@ class OptimizedKeypointsDataset(Dataset):
         self._image_cache = LRUCache(maxsize=cache_size) if enable_caching else None
         self.transform = transform or ITransform(img_size=img_size, clip_limit=1.5, tile_size=(8, 8),
                                                  grayscale=grayscale, device=self.device)
-        self.augmentation = augmentation if split == "train" else None
-        if self.augmentation is not None:
-            raise NotImplementedError("training augmentation is out of scope for the MI355X data path")
+        self.augmentation = augmentation if split == "train" else None   # other splits ignore it
         self._validate_dataset_structure()
         self.img_files, self.label_files = self._load_file_pairs()
         logger.info(f"Loaded {len(self.img_files)} images with valid labels for {split} split")
@@ -222,7 +223,11 @@ class OptimizedKeypointsDataset(Dataset):
 
     # ---- sample
     def _apply_transformations(self, image_data: ImageData, ann: AnnotationData):
-        return self.transform.transform(image_data.image), ann
+        image = image_data.image
+        if self.augmentation and self.split == "train":
+            image, kp, vis, boxes = self.augmentation(image, ann.keypoints, ann.visibilities, ann.bboxes)
+            ann = AnnotationData(kp, vis, ann.classes, boxes)
+        return self.transform.transform(image), ann
 
     def _generate_training_targets(self, ann: AnnotationData) -> torch.Tensor:
         heat = generate_target_heatmap(ann.keypoints.to(self.device), self.heatmap_size, sigma=3.0)
@@ -322,12 +327,13 @@ def create_optimized_dataloader(dataset_dir: str, batch_size: int = 32, num_work
                                 img_size: int = 224, grayscale: bool = True, num_keypoints: int = 17,
                                 heatmap_size: Tuple[int, int] = (56, 56), max_persons: int = 10,
                                 enable_caching: bool = True, cache_size: int = 1000,
-                                device: Union[str, torch.device] = "cuda") -> DataLoader:
-    """Reference :562-612 (same arguments; ``device`` added)."""
+                                device: Union[str, torch.device] = "cuda", augmentation=None) -> DataLoader:
+    """Reference :562-612 (same arguments; ``device`` and ``augmentation`` added:
+    a ``KeypointAugmentation`` applied to the train split)."""
     ds = OptimizedKeypointsDataset(dataset_dir=dataset_dir, split=split, img_size=img_size, grayscale=grayscale,
                                    num_keypoints=num_keypoints, heatmap_size=heatmap_size,
                                    max_persons=max_persons, enable_caching=enable_caching, cache_size=cache_size,
-                                   device=device)
+                                   device=device, augmentation=augmentation)
     nw = _workers(num_workers, ds.device)
     kw = dict(batch_size=batch_size, shuffle=(split == "train"), num_workers=nw, pin_memory=False,
               drop_last=(split == "train"), collate_fn=efficient_collate_fn, persistent_workers=nw > 0)
