@@ -653,6 +653,59 @@ int kpd_conv3x3_forward(const float* x, const float* w, const float* b, int N, i
 int kpd_conv3x3_backward(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
                          float* gx, float* gw, float* gb, void* stream);
 
+/* Training side: nn.BatchNorm2d in train mode (batch statistics) fused with
+ * the ReLU and the Dropout2d that follow it in the heatmap head's
+ * deconv_layers and final_layer (heatmap_head.py:31-45,55-66), forward and
+ * backward.  NCHW fp32 device tensors, the layout the conv3x3
+ * entries above take and return.  gamma, beta: [C] or NULL (1 / 0); drop:
+ * [N][C] multiplier per (image, channel) plane or NULL (1) -- Dropout2d with
+ * rate p is a multiplier of 0 or 1 / (1 - p), drawn by the caller.  With
+ * n = N * H * W values per channel:
+ *
+ * Statistics: mean_c = sum x / n, var_c = sum (x - mean_c)^2 / n (biased),
+ * invstd_c = 1 / sqrt(var_c + eps): sums and these three in double;
+ * save_mean [C] and save_invstd [C] are their fp32 roundings.  The summation
+ * order depends on (N, C, H, W) alone (no atomics, no partition that depends
+ * on the device's state): two calls on the same inputs are bit-identical, in
+ * every output of both entries.
+ * Running statistics (running_mean, running_var: [C] in/out, both or neither
+ * NULL): rm <- (1 - momentum) rm + momentum mean_c, rv <- (1 - momentum) rv +
+ * momentum var_c n / (n - 1) (the unbiased variance, as F.batch_norm), in
+ * double, stored as fp32.
+ * Forward, per element in fp32: xhat = (x - save_mean_c) * save_invstd_c,
+ * pre = fmaf(xhat, gamma_c, beta_c), y = (flags & KPD_BN_RELU ? max(pre, 0) :
+ * pre) * drop[n][c].
+ * Backward, for gy = dL/dy: g = gy * drop[n][c] * [pre > 0] (the last factor
+ * with KPD_BN_RELU only; xhat and pre recomputed from x by the forward's own
+ * code, so the mask is bitwise the forward's); gbeta_c = sum g and ggamma_c =
+ * sum g * xhat in double in a fixed order, stored as fp32; gx = gamma_c
+ * invstd_c (g - gbeta_c / n - xhat ggamma_c / n), the three per-channel
+ * coefficients gamma_c invstd_c, gbeta_c / n, ggamma_c / n prepared in double
+ * (the two means carried as fp32 hi + lo pairs, so that sum gx over a channel
+ * keeps no common rounding shift) and the element arithmetic in fp32.  gx,
+ * ggamma, gbeta are each nullable
+ * (gx alone may be requested); flags, gamma, beta, drop and the save buffers
+ * are the forward's.
+ *
+ * Two passes each way -- statistics then apply (x read twice, y written),
+ * reduce then apply (x and gy read twice, gx written) -- with 16-byte accesses
+ * when H * W % 4 == 0 and the tensors are 16-byte aligned, one value per
+ * access otherwise.  Scratch (per-workgroup double partials) comes from the
+ * stream-ordered allocator; no host synchronisation.
+ *
+ * Arguments are checked before any device work; a failure is KPD_EINVAL with
+ * the argument named: N, C, H, W >= 1; n > 1 ("expected more than 1 value per
+ * channel", torch's ValueError); eps > 0; momentum in [0, 1]; x, y, gy and the
+ * save buffers non-null; the running pointers both given or both NULL; y does
+ * not overlap x (the backward reads x again); gx overlaps neither x nor gy. */
+#define KPD_BN_RELU 1
+int kpd_bn_train_forward(const float* x, int N, int C, int H, int W, const float* gamma, const float* beta,
+                         const float* drop, float eps, float momentum, float* running_mean, float* running_var,
+                         int flags, float* y, float* save_mean, float* save_invstd, void* stream);
+int kpd_bn_train_backward(const float* x, const float* gy, int N, int C, int H, int W, const float* gamma,
+                          const float* beta, const float* drop, const float* save_mean, const float* save_invstd,
+                          int flags, float* gx, float* ggamma, float* gbeta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,7 +277,14 @@ __global__ __launch_bounds__(256) void k6_max_kernel(const float* __restrict__ w
 // w [O][C][3][3] -> split weights [co'][9][ci'] as [hi32 | lo32] groups scaled
 // 2^w_exp, w_exp = split_exp_of(max |w|) (pack_split_hm's layout), rows
 // co' >= cout zero up to cout_p; flip: the dgrad conv's weights, co' = c,
-// ci' = o, tap t <- 8 - t (d(8 - t) = -d(t))
+// ci' = o, tap t <- 8 - t (d(8 - t) = -d(t)).  Odd rows co' carry -w (and
+// k6_bias_sign_kernel's -b): k6_nhwc_nchw_kernel negates those channels
+// back.  The f16 MFMA's accumulation leaves an error of one sign, whatever
+// the sign of the value (measured: mean -0.10 x the rms error at K = 9 * 256,
+// uncorrelated with the value); with the sign alternating over the output
+// channels it no longer adds up in a sum over channels, as the gradient of
+// anything in front of the first conv takes of this dgrad.  An even channel's
+// value is unchanged, an odd one's error is mirrored.
 __global__ __launch_bounds__(256) void k6_pack_w_kernel(const float* __restrict__ w, int O, int C, int flip,
                                                         const float* __restrict__ wmax, int cout_p,
                                                         _Float16* __restrict__ ws) {
@@ -289,14 +296,23 @@ __global__ __launch_bounds__(256) void k6_pack_w_kernel(const float* __restrict_
   const long r = i / cin;
   const int t = (int)(r % 9), co = (int)(r / 9);
   const float v = co >= cout ? 0.f : flip ? w[((size_t)ci * C + co) * 9 + (8 - t)] : w[((size_t)co * C + ci) * 9 + t];
-  const float xs = ldexpf(v, w_exp);
+  const float xs = ldexpf((co & 1) ? -v : v, w_exp);
   const _Float16 hi = (_Float16)xs, lo = (_Float16)(xs - (float)hi);
   const size_t o = (size_t)r * 2 * cin + (size_t)(ci / 32) * 64 + ci % 32;
   ws[o] = hi;
   ws[o + 32] = lo;
 }
 
-// [N][3136][Op] (the first O of Op channels) -> [N][O][3136]
+// the bias padded to the tile's cout_p columns (zero without one: dgrad), odd entries negated
+__global__ __launch_bounds__(256) void k6_bias_sign_kernel(const float* __restrict__ b, int cout, int cout_p,
+                                                           float* __restrict__ out) {
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= cout_p) return;
+  const float v = (b && o < cout) ? b[o] : 0.f;
+  out[o] = (o & 1) ? -v : v;
+}
+
+// [N][3136][Op] (the first O of Op channels) -> [N][O][3136], odd channels negated back
 __global__ __launch_bounds__(256) void k6_nhwc_nchw_kernel(const float* __restrict__ in, int O, int Op,
                                                            float* __restrict__ out) {
   __shared__ float t[64][65];
@@ -309,7 +325,7 @@ __global__ __launch_bounds__(256) void k6_nhwc_nchw_kernel(const float* __restri
   __syncthreads();
   for (int i = tid; i < 64 * 64; i += 256) {
     const int oo = i >> 6, pp = i & 63;
-    if (p0 + pp < HW && o0 + oo < O) out[((size_t)n * O + o0 + oo) * HW + p0 + pp] = t[pp][oo];
+    if (p0 + pp < HW && o0 + oo < O) out[((size_t)n * O + o0 + oo) * HW + p0 + pp] = (oo & 1) ? -t[pp][oo] : t[pp][oo];
   }
 }
 
@@ -618,11 +634,8 @@ static hipError_t k6_split_conv(const float* x, const float* w, const float* b, 
   do {
     hipLaunchKernelGGL(k6_hm_border_kernel, dim3((unsigned)N), dim3(256), 0, st, hm, cin);
     if ((e = hipMemsetAsync(hsc, 0, (size_t)N * 16, st)) != hipSuccess) break;
-    if (!b || cout_p != cout) {   // the bias padded to the tile's columns (zero for dgrad)
-      if ((e = hipMemsetAsync(zb, 0, (size_t)cout_p * 4, st)) != hipSuccess) break;
-      if (b && (e = hipMemcpyAsync(zb, b, (size_t)cout * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) break;
-      b = zb;
-    }
+    hipLaunchKernelGGL(k6_bias_sign_kernel, dim3((unsigned)((cout_p + 255) / 256)), dim3(256), 0, st, b, cout, cout_p, zb);
+    b = zb;
     const long per_img = (long)cin * kHmSide * kHmSide;
     hipLaunchKernelGGL(k6_amax_kernel, dim3(64, (unsigned)N), dim3(256), 0, st, x, per_img, hsc);
     if ((e = hipGetLastError()) != hipSuccess) break;

@@ -34,7 +34,8 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
-           "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch")
+           "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
+           "kpd_bn_train_backward")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -67,6 +68,7 @@ FLAG_DUAL_HEAD = 2
 FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default: only the ROI-align footprints
 FPN_IN_CHANNELS = (16, 24, 48, 576)   # LightweightFPN's lateral input widths (backbone.py)
 HEAD_CHANNEL_ATT, HEAD_SPATIAL_ATT, HEAD_CONVS, HEAD_ALL = 1, 2, 4, 7
+BN_RELU = 1            # KPD_BN_RELU
 DECODE_ARGMAX, DECODE_SUBPIXEL, DECODE_SOFTARGMAX, DECODE_MODEL = 0, 1, 2, 3
 STAGES = ("body", "fpn_lateral", "fpn0", "topk", "person_detect", "roi_align", "hm_attention", "hm_conv1",
           "hm_conv2", "hm_conv3", "hm_final_decode", "keypoint_head")
@@ -161,6 +163,10 @@ def load() -> ctypes.CDLL:
                                         c_void_p]
     lib.kpd_conv3x3_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p]
+    lib.kpd_bn_train_forward.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                         c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kpd_bn_train_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
@@ -514,6 +520,66 @@ def conv3x3_backward(x: torch.Tensor, weight: torch.Tensor, grad_y: torch.Tensor
         check(lib.kpd_conv3x3_backward(_ptr(x), _ptr(w), _ptr(gy), N, C, H, W, O, _ptr(gx), _ptr(gw), _ptr(gb),
                                        _stream(x.device)), "kpd_conv3x3_backward")
     return gx, gw, gb
+
+
+def _bn_vec(t: Optional[torch.Tensor], n: int, name: str, device: torch.device) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.detach().to(device, torch.float32).contiguous()
+    if t.numel() != n:
+        raise ValueError(f"{name} must hold {n} values, got {tuple(t.shape)}")
+    return t
+
+
+def bn_train_forward(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
+                     drop: Optional[torch.Tensor], eps: float, momentum: float,
+                     running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], relu: bool = True):
+    """Batch-statistics BatchNorm2d + ReLU + per-(image, channel) multiplier on
+    NCHW device tensors (kpd_bn_train_forward): (y, save_mean, save_invstd).
+    running_mean / running_var ([C] fp32, contiguous, on x's device) are
+    updated in place through their pointers; the caller bumps their versions."""
+    x = _dev_f32(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [N, C, H, W], got {tuple(x.shape)}")
+    N, C, H, W = x.shape
+    g, b = _bn_vec(gamma, C, "weight", x.device), _bn_vec(beta, C, "bias", x.device)
+    d = _bn_vec(drop, N * C, "drop", x.device)
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and (t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() != C):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of {C} values on {x.device}")
+    y = torch.empty_like(x)
+    mean = torch.empty(C, device=x.device)
+    invstd = torch.empty(C, device=x.device)
+    with torch.cuda.device(x.device):
+        check(load().kpd_bn_train_forward(_ptr(x), N, C, H, W, _ptr(g), _ptr(b), _ptr(d), float(eps), float(momentum),
+                                          _ptr(running_mean), _ptr(running_var), BN_RELU if relu else 0, _ptr(y),
+                                          _ptr(mean), _ptr(invstd), _stream(x.device)), "kpd_bn_train_forward")
+    return y, mean, invstd
+
+
+def bn_train_backward(x: torch.Tensor, grad_y: torch.Tensor, gamma: Optional[torch.Tensor],
+                      beta: Optional[torch.Tensor], drop: Optional[torch.Tensor], save_mean: torch.Tensor,
+                      save_invstd: torch.Tensor, relu: bool = True, need_x: bool = True, need_gamma: bool = True,
+                      need_beta: bool = True):
+    """Gradients of bn_train_forward (kpd_bn_train_backward): (gx, ggamma,
+    gbeta), None where not requested."""
+    x = _dev_f32(x, "x")
+    N, C, H, W = x.shape
+    gy = _dev_f32(grad_y, "grad_y")
+    if tuple(gy.shape) != (N, C, H, W):
+        raise ValueError(f"grad_y must be [{N}][{C}][{H}][{W}], got {tuple(gy.shape)}")
+    g, b = _bn_vec(gamma, C, "weight", x.device), _bn_vec(beta, C, "bias", x.device)
+    d = _bn_vec(drop, N * C, "drop", x.device)
+    mean, invstd = _bn_vec(save_mean, C, "save_mean", x.device), _bn_vec(save_invstd, C, "save_invstd", x.device)
+    gx = torch.empty_like(x) if need_x else None
+    gg = torch.empty(C, device=x.device) if need_gamma else None
+    gb = torch.empty(C, device=x.device) if need_beta else None
+    with torch.cuda.device(x.device):
+        check(load().kpd_bn_train_backward(_ptr(x), _ptr(gy), N, C, H, W, _ptr(g), _ptr(b), _ptr(d), _ptr(mean),
+                                           _ptr(invstd), BN_RELU if relu else 0, _ptr(gx), _ptr(gg), _ptr(gb),
+                                           _stream(x.device)), "kpd_bn_train_backward")
+    return gx, gg, gb
 
 
 class PlanCache:

@@ -9,6 +9,15 @@ three 3x3 convs on MFMA and the fused final 1x1 + sigmoid, kpd_heatmap_head):
 the module packs its own weights into a plan under the model's
 ``heatmap_head.`` prefix.  The decoders are device kernels
 (kpd_decode_heatmaps).  There is no CPU fallback: CPU inputs raise.
+
+In train mode (``head.train()``) the forward is composed of differentiable
+pieces instead of the plan: the two attention blocks in torch ops, every 3x3
+convolution through ``dll.ops.conv3x3`` and every BatchNorm2d + ReLU +
+Dropout2d through ``dll.ops.bn_relu_dropout2d`` (batch statistics, running
+statistics updated; both native forward and backward), the final 1x1
+convolution and the sigmoid in torch ops.  ``loss.backward()`` and an
+optimiser step then work on the head, and ``eval()`` afterwards serves the
+updated weights and running statistics through the plan.
 """
 import ctypes
 import weakref
@@ -16,8 +25,10 @@ from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _native
+from ..ops import bn_relu_dropout2d, conv3x3
 from ..configs.model_config import HeatmapHeadConfig
 
 
@@ -34,6 +45,9 @@ class ChannelAttention(nn.Module):
         self._owner = None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.training:   # torch ops with autograd (the train path of HeatmapHead)
+            cw = torch.sigmoid(self.fc(self.avg_pool(x).flatten(1)) + self.fc(self.max_pool(x).flatten(1)))
+            return cw.view(x.size(0), -1, 1, 1)
         head = _owner(self)
         _, cw, _ = head._plan(x.device).heatmap_head(x, _native.HEAD_CHANNEL_ATT)
         return cw.view(x.size(0), -1, 1, 1)
@@ -48,6 +62,14 @@ class SpatialAttention(nn.Module):
         self._owner = None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.training:   # torch ops with autograd (the train path of HeatmapHead)
+            pooled = torch.cat([x.mean(dim=1, keepdim=True), x.max(dim=1, keepdim=True)[0]], dim=1)
+            # the 7x7 conv as unfold + matmul: the framework's own convolution backward is not
+            # bit-reproducible from run to run on the device, a matmul's is
+            k, pad = self.conv.kernel_size, self.conv.padding
+            cols = F.unfold(pooled, k, padding=pad)                          # [B, 2 * k * k, H * W]
+            pre = torch.matmul(self.conv.weight.view(1, -1), cols) + self.conv.bias.view(1, 1, 1)
+            return torch.sigmoid(pre).view(x.size(0), 1, x.size(2), x.size(3))
         head = _owner(self)
         _, _, sw = head._plan(x.device).heatmap_head(x, _native.HEAD_SPATIAL_ATT)
         return sw.unsqueeze(1)
@@ -91,17 +113,66 @@ class HeatmapHead(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         self._plans = _native.PlanCache("heatmap_head.")
+        # inspection hook of the train path (the analogue of kpd_debug_copy's "tap0".."tap3"): when this
+        # is a list, a train-mode forward appends its three post-activation tensors to it, detached
+        self.train_taps = None
 
     def _plan(self, device: torch.device) -> "_native.Plan":
         if self.training:
-            raise NotImplementedError("HeatmapHead runs the eval path only (BatchNorm running statistics, no "
-                                      "dropout); call .eval()")
+            raise NotImplementedError("the native plan serves the eval path only (BatchNorm running statistics, "
+                                      "no dropout); a train-mode forward does not go through it")
         return self._plans.get(self, device, self.precision)
+
+    def _conv_bn_relu(self, x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, p: float) -> torch.Tensor:
+        """conv3x3 -> batch-statistics BN -> ReLU -> Dropout2d(p), as nn.BatchNorm2d
+        and nn.Dropout2d behave in train mode; both operators native."""
+        x = conv3x3(x, conv.weight, conv.bias)
+        momentum = 0.0 if bn.momentum is None else bn.momentum
+        if bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+            if bn.momentum is None:   # cumulative moving average
+                momentum = 1.0 / float(bn.num_batches_tracked)
+        drop = None
+        if p > 0:
+            drop = torch.empty(x.size(0), x.size(1), device=x.device)
+            drop = drop.bernoulli_(1 - p).div_(1 - p) if p < 1 else drop.zero_()
+        x = bn_relu_dropout2d(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
+                              bn.running_var if bn.track_running_stats else None, momentum=momentum, eps=bn.eps,
+                              relu=True, drop=drop)
+        if isinstance(self.train_taps, list):
+            self.train_taps.append(x.detach())
+        return x
+
+    def _forward_train(self, x: torch.Tensor):
+        """The train path: fp32-accurate whatever ``precision`` says (the native
+        3x3 convolutions are the split-product ones of dll.ops.conv3x3, the
+        rest is fp32)."""
+        _native._require_cuda(x, "x")
+        x = x.float()
+        att = None
+        if self.config.use_attention:
+            cw = self.channel_attention(x)
+            x = x * cw
+            sw = self.spatial_attention(x)
+            x = x * sw
+            att = (cw, sw)
+        mods = list(self.deconv_layers)
+        for i in range(0, len(mods), 4):
+            x = self._conv_bn_relu(x, mods[i], mods[i + 1], mods[i + 3].p)
+        conv, bn, _, last = self.final_layer
+        x = self._conv_bn_relu(x, conv, bn, 0.0)
+        R, Ch, H, W = x.shape
+        w = last.weight.view(last.weight.size(0), Ch)
+        heat = torch.matmul(w, x.view(R, Ch, H * W)) + last.bias.view(1, -1, 1)   # the 1x1 conv
+        return torch.sigmoid(heat).view(R, -1, H, W), att
 
     def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, Optional[Tuple[torch.Tensor, torch.Tensor]]]:
         """x [B, 64, 56, 56] ROI features -> (heatmaps [B, 17, 56, 56] in (0, 1),
         (channel weights [B, 64, 1, 1], spatial weights [B, 1, 56, 56]) or None
-        without attention) -- reference :81-113."""
+        without attention) -- reference :81-113.  In train mode: the same
+        tuple from the differentiable train path (module docstring)."""
+        if self.training:
+            return self._forward_train(x)
         parts = _native.HEAD_ALL if self.config.use_attention else _native.HEAD_CONVS
         heat, cw, sw = self._plan(x.device).heatmap_head(x, parts)
         att = (cw.view(x.size(0), -1, 1, 1), sw.unsqueeze(1)) if self.config.use_attention else None

@@ -11,12 +11,22 @@ reference gets these gradients from autograd in Trainer.train
 
     from dll.ops import conv3x3
     y = conv3x3(x, conv.weight, conv.bias)     # == F.conv2d(x, w, b, padding=1)
+
+and the train-mode BatchNorm2d + ReLU + Dropout2d that follows each of them
+(libkpd: kpd_bn_train_forward / kpd_bn_train_backward):
+
+    from dll.ops import bn_relu_dropout2d
+    y = bn_relu_dropout2d(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                          momentum=bn.momentum, eps=bn.eps, drop=mask)
+    # == F.relu(F.batch_norm(x, rm, rv, w, b, True, momentum, eps)) * mask[:, :, None, None]
 """
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
+
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -46,3 +56,51 @@ class Conv3x3Function(torch.autograd.Function):
 def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.conv2d(x, weight, bias, padding=1) with a native forward and backward."""
     return Conv3x3Function.apply(x, weight, bias)
+
+
+class BnReluDropout2dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, drop):
+        y, mean, invstd = _native.bn_train_forward(x, weight, bias, drop, eps, momentum, running_mean, running_var,
+                                                   relu)
+        # the native call wrote the running statistics through raw pointers: bump their
+        # version counters, which PlanCache keys on (a later eval() forward repacks)
+        for t in (running_mean, running_var):
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+        ctx.relu = bool(relu)
+        ctx.dtypes = (x.dtype, None if weight is None else weight.dtype, None if bias is None else bias.dtype)
+        if any(ctx.needs_input_grad[:3]):   # nothing is kept under torch.no_grad()
+            ctx.save_for_backward(x, weight, bias, drop, mean, invstd)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y: torch.Tensor):
+        x, weight, bias, drop, mean, invstd = ctx.saved_tensors
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        gx, gg, gb = _native.bn_train_backward(x, grad_y, weight, bias, drop, mean, invstd, ctx.relu, need_x=nx,
+                                               need_gamma=nw and weight is not None,
+                                               need_beta=nb and bias is not None)
+        if gx is not None:
+            gx = gx.to(ctx.dtypes[0])
+        if gg is not None:
+            gg = gg.to(ctx.dtypes[1]).view_as(weight)
+        if gb is not None:
+            gb = gb.to(ctx.dtypes[2]).view_as(bias)
+        return gx, gg, gb, None, None, None, None, None, None
+
+
+def bn_relu_dropout2d(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                      running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], *,
+                      momentum: float = 0.1, eps: float = 1e-5, relu: bool = True,
+                      drop: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Batch-statistics batch norm of x [N, C, H, W], then ReLU (``relu``), then
+    the per-plane multiplier ``drop`` [N, C] (Dropout2d with rate p: 0 or
+    1 / (1 - p)); native forward and backward.  running_mean / running_var
+    (both or neither; [C] fp32 on x's device) are updated in place with
+    ``momentum`` as F.batch_norm does, also under torch.no_grad()."""
+    if drop is not None and (drop.dim() != 2 or tuple(drop.shape) != tuple(x.shape[:2])):
+        raise ValueError(f"drop must be [N, C] = {list(x.shape[:2])}, got {list(drop.shape)}")
+    return BnReluDropout2dFunction.apply(x, weight, bias, running_mean, running_var, float(momentum), float(eps),
+                                         bool(relu), drop)
