@@ -263,6 +263,29 @@ int kpd_draw_poses(uint8_t* const* images, const int* heights, const int* widths
  * (the kernel table is staged from host memory). */
 int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, float sigma, float* out, void* stream);
 
+/* Per-ROI training targets of the top-down HeatmapHead: the
+ * person's own joints placed in the frame the head predicts in, by the
+ * convention of the decoders and convert_to_original_coords (map pixel i
+ * stands for i / (W - 1) of the unclamped box).  kpts [R][K][2]
+ * image-normalised (x, y), vis [R][K], boxes [R][4] (cx, cy, w, h), all device
+ * fp32; rows [n] int32 (device) selects and orders the ROIs, NULL = 0..n-1.
+ * For output row j, r = rows[j], joint k, in fp32 without contraction:
+ *   bx = cx - w/2, by = cy - h/2;  u = (x - bx) / w, v = (y - by) / h
+ *   on = w > 0 && h > 0 && vis > 0 && 0 <= u <= 1 && 0 <= v <= 1
+ *        (a NaN anywhere makes it false)
+ *   weight[j][k] = on ? 1 : 0;  px = u * (W - 1), py = v * (H - 1)
+ *   heat[j][k][y][x] = on ? expf(-((x - px)^2 + (y - py)^2) / (2 sigma^2)) : 0
+ * i.e. the Gaussian of the reference's _convert_keypoints_to_heatmaps (sigma
+ * 2 there): peak 1 at a sub-pixel centre, no cut-off.  heat [n][K][H][W],
+ * weight [n][K] (the loss's target_weight).  KPD_EINVAL before any device
+ * work: a null pointer with n > 0, n < 0, H or W < 2, K <= 0, sigma not
+ * positive and finite, n > R without a row list.  Every rows[j] must lie in
+ * [0, R): that is the caller's contract, the values are on the device and are
+ * not checked.  n = 0 returns KPD_OK without a launch.  One launch; no
+ * synchronisation, no allocation, no host table. */
+int kpd_roi_targets(const float* kpts, const float* vis, const float* boxes, const int32_t* rows, int n, int R, int K,
+                    int H, int W, float sigma, float* heat, float* weight, void* stream);
+
 /* Validation metrics: Trainer._calculate_validation_metrics
  * (dll/training/trainer.py:384-429).  pred, gt: [n][2], vis: [n] (device);
  * thresholds: host array (<= 16).  out (device) = [ADE, PCK_t...]: ADE = mean
@@ -604,6 +627,25 @@ int kpd_backbone_body(kpd_plan* plan, const float* image, int B, int C, int H, i
  * (3x3 + BN + ReLU) of lateral i, exact fp32 products. */
 int kpd_backbone_fpn(kpd_plan* plan, const float* feat0, const float* feat1, const float* feat2, const float* feat3,
                      int B, const int* sizes, float* out0, float* out1, float* out2, float* out3, void* stream);
+
+/* The trunk's ROI features, exactly as the fused forward serves them to
+ * HeatmapHead: the stages of a kpd_forward pass with flags 0
+ * up to and including the ROI align -- body, laterals, level 0 (on the ROI
+ * footprints where the forward takes that path), top-k, slot map, ROI align --
+ * and no head.  image [B][C][H][W], boxes [B][P][4] (cx, cy, w, h; P > 0), as
+ * kpd_forward takes them; rows [n] int32 (device), ascending indices into B*P,
+ * selects ROIs, NULL = all B*P (then n must equal B*P).  out [n][64][56][56]
+ * NCHW = the selected rows of the pass's ROI buffer (debug buffer "roi",
+ * [B*P][56][56][64]), bit for bit.  A row index outside [0, B*P) is skipped
+ * (its output row is left unwritten).  Batches above the pass limit run as
+ * consecutive passes on the caller's stream in workspace slot 0; no sub-batch
+ * streams, never captured into a graph, no synchronisation.  It shares the
+ * plan's workspace with kpd_forward and leaves it as a forward of the same
+ * shapes would (debug buffers are dropped); needs the backbone, fpn and
+ * channel_attention weights, not the heads'.  Arguments are validated as
+ * kpd_forward's are. */
+int kpd_roi_features(kpd_plan* plan, const float* image, int B, int C, int H, int W, const float* boxes, int P,
+                     const int32_t* rows, int n, float* out, void* stream);
 
 /* ChannelAttention.forward (keypoint_model.py:33-44) on x [B][128][H][W] ->
  * scores [B][128] (sigmoid); select_top_k_channels (:653-661): topk [B][k]

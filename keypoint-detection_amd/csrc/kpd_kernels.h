@@ -501,6 +501,10 @@ hipError_t launch_roi_align_nchw(const float* feat, int C, int H, int W, const f
 hipError_t launch_nchw_rows_to_nhwc(const float* in, int N, int C, int H, int W, float* out, float* stats,
                                     hipStream_t st, float* amax = nullptr, int amax_stride = 0);
 hipError_t launch_nhwc_to_nchw(const float* in, int N, int HW, int C, float* out, hipStream_t st);
+// gathering [R][HW][64] -> [n][64][HW]: out[j] = in[rows[j] - r0] (rows null: in[j - r0]) where that row
+// lies in [0, R); other output rows are left untouched
+hipError_t launch_nhwc64_rows_to_nchw(const float* in, int R, int HW, const int32_t* rows, int r0, int n, float* out,
+                                      hipStream_t st);
 // padded-channel NHWC <-> NCHW (any C <= Cp; the padding channels written as zero)
 hipError_t launch_nhwc_pad_to_nchw(const float* in, int N, int HW, int C, int Cp, float* out, hipStream_t st);
 hipError_t launch_nchw_to_nhwc_pad(const float* in, int N, int HW, int C, int Cp, float* out, hipStream_t st);

@@ -1599,6 +1599,52 @@ int kpd_backbone(kpd_plan* p, const float* image, int B, int C, int H, int W, fl
   return KPD_OK;
 }
 
+// The trunk's ROI features as the fused forward serves them to HeatmapHead:
+// forward_one's stages up to and including stage_roi on a flags-0 pass, then
+// the selected rows of w.roi (NHWC) gathered to `out` (NCHW).  Eager, on the
+// caller's stream, in workspace 0; the host-side workspace state (sc_dirty
+// through stage_body / stage_topk, the carve through begin_pass) moves exactly
+// as in a forward of the same shapes, so later forwards and graph replays see
+// what they expect.
+int kpd_roi_features(kpd_plan* p, const float* image, int B, int C, int H, int W, const float* boxes, int P,
+                     const int32_t* rows, int n, float* out, void* stream) {
+  // kpd_forward's argument checks, ahead of the plan's state (they need no device)
+  if (!p) return fail(KPD_EINVAL, "null plan");
+  if (!image || B <= 0 || H < 32 || W < 32) return fail(KPD_EINVAL, "bad image shape");
+  if (C != p->in_ch) return fail(KPD_EINVAL, "image channels do not match backbone in_channels");
+  if (P <= 0 || !boxes) return fail(KPD_EINVAL, "boxes must be [B][P>0][4]");
+  if ((long)B * P > 0x7fffffffL) return fail(KPD_EINVAL, "boxes: too many ROIs");
+  if (n < 0 || (!rows && n != B * P)) return fail(KPD_EINVAL, "n must be the length of rows, or B*P without rows");
+  if (n > 0 && !out) return fail(KPD_EINVAL, "null output pointer");
+  if (!p->finalized) return fail(KPD_ESTATE, "plan not finalized");
+  if (!p->has_body || !p->has_fpn || !p->has_ca)
+    return fail(KPD_ESTATE, "plan lacks backbone / fpn / channel_attention weights");
+  if (n == 0) return KPD_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->device));
+  p->debug.clear();   // they point into the workspace this call rewrites
+  if (p->path_on) p->path.e.clear();
+  const FwdArgs a{image, B, C, H, W, const_cast<float*>(boxes), B, P, 0,
+                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const int cap = max_pass_images(H, W), npass = (B + cap - 1) / cap;
+  for (int q = 0; q < npass; ++q) {
+    const int b0 = (int)((long)B * q / npass), b1 = (int)((long)B * (q + 1) / npass);
+    const FwdArgs s = a.images(b0, b1);
+    const PathScope path_scope(p);
+    Pass ps;
+    const float* taps[4] = {};
+    if (int rc = begin_pass(ps, p, 0, false, s.B, H, W, s.NB, P, 0, st)) return rc;
+    if (int rc = stage_body(ps, s.image, C, taps)) return rc;
+    if (int rc = stage_laterals(ps, taps, false)) return rc;
+    if (int rc = stage_level0(ps, level0_footprint(ps, s) ? &s : nullptr)) return rc;
+    if (int rc = stage_topk(ps, s)) return rc;
+    if (int rc = stage_roi(ps, s, false)) return rc;
+    // rows of other passes fail the kernel's range test; without a row list output row j is ROI j
+    HIP_TRY(launch_nhwc64_rows_to_nchw(ps.w->roi, s.NB * P, 3136, rows, b0 * P, n, out, st));
+  }
+  return KPD_OK;
+}
+
 int kpd_backbone_body(kpd_plan* p, const float* image, int B, int C, int H, int W, float* feat0, float* feat1,
                       float* feat2, float* feat3, void* stream) {
   if (!p || !p->finalized) return fail(KPD_ESTATE, "plan not finalized");

@@ -236,6 +236,35 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
   }
 }
 
+// Gathering [R][HW][64] -> [n][64][HW]: output row j is input row rows[j] - r0
+// (rows null: j), written only when that lies in [0, R) -- a pass of a larger
+// batch holds rows r0 .. r0 + R - 1 and leaves the others to its neighbours.
+// 64 pixels x 64 channels per workgroup through LDS: the tile is 16 KiB
+// contiguous on the NHWC side (float4 loads), and each channel's 64 pixels are
+// 256 contiguous bytes on the NCHW side; the odd LDS pitch keeps both the row
+// writes and the column reads off a common bank.
+__global__ __launch_bounds__(256) void nhwc64_rows_to_nchw_kernel(const float* __restrict__ in, int R, int HW,
+                                                                  const int32_t* __restrict__ rows, int r0,
+                                                                  float* __restrict__ out) {
+  __shared__ float t[64][65];
+  const int tiles = (HW + 63) / 64, j = blockIdx.x / tiles, tid = threadIdx.x;
+  const int p0 = (blockIdx.x - j * tiles) * 64, np = min(64, HW - p0);
+  const long r = (rows ? (long)rows[j] : (long)j) - r0;
+  if (r < 0 || r >= R) return;   // (uniform over the workgroup)
+  const float4* src = reinterpret_cast<const float4*>(in + ((size_t)r * HW + p0) * 64);
+  for (int e = tid; e < np * 16; e += 256) {
+    const float4 v = src[e];
+    const int p = e >> 4, c = (e & 15) * 4;
+    t[p][c] = v.x; t[p][c + 1] = v.y; t[p][c + 2] = v.z; t[p][c + 3] = v.w;
+  }
+  __syncthreads();
+  float* dst = out + (size_t)j * 64 * HW + p0;
+  for (int e = tid; e < 64 * 64; e += 256) {
+    const int c = e >> 6, p = e & 63;
+    if (p < np) dst[(size_t)c * HW + p] = t[p][c];
+  }
+}
+
 // [N][HW][Cp] (channels padded to Cp) -> [N][C][HW]: a 32-pixel x 32-channel
 // tile per workgroup (grid: pixel tiles, channel tiles, images); the body taps
 // of MobileNetV3Wrapper.body (up to 576 channels)
@@ -381,6 +410,15 @@ hipError_t launch_nhwc_to_nchw(const float* in, int N, int HW, int C, float* out
   if (N <= 0 || HW <= 0) return hipSuccess;
   if (C > 128) return hipErrorInvalidValue;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((HW + 31) / 32, N), dim3(256), 0, st, in, HW, C, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_nhwc64_rows_to_nchw(const float* in, int R, int HW, const int32_t* rows, int r0, int n, float* out,
+                                      hipStream_t st) {
+  if (n <= 0 || R <= 0 || HW <= 0) return hipSuccess;
+  const long blocks = (long)n * ((HW + 63) / 64);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(nhwc64_rows_to_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, R, HW, rows, r0, out);
   return hipGetLastError();
 }
 

@@ -6,9 +6,10 @@ the training augmentation ``KeypointAugmentation`` / ``augment_batch``: flip,
 rotate, scale with the labels moved along by ``kpd_augment_batch``),
 ``dll.losses``, ``dll.ops`` and ``dll.utils`` (metrics and ``draw_poses``, the
 pose overlay the prediction CLI saves: boxes, skeleton, joints and a heatmap
-underlay drawn in place by ``kpd_draw_poses``).  The training loop,
-feature-map plotting and the reference's matplotlib panels are out of scope
-(DESIGN.md §8).
+underlay drawn in place by ``kpd_draw_poses``) and ``dll.training`` (the
+``Trainer`` of the heatmap head on frozen trunk features).
+Training anything but the heatmap head, feature-map plotting and the
+reference's matplotlib panels are out of scope.
 """
 from .configs import ModelConfig, TrainingConfig
 from .models import MultiPersonKeypointModel

@@ -35,7 +35,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
-           "kpd_bn_train_backward")
+           "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -167,6 +167,10 @@ def load() -> ctypes.CDLL:
                                          c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kpd_bn_train_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kpd_roi_targets.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p, c_void_p, c_void_p]
+    lib.kpd_roi_features.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
@@ -353,6 +357,32 @@ class Plan:
                                                  _ptr(sel), _stream(self.device)), "kpd_channel_attention")
         return scores, topk.long(), sel
 
+    def roi_features(self, image: torch.Tensor, boxes: torch.Tensor, rows=None) -> torch.Tensor:
+        """The trunk's ROI features as the fused forward serves them to
+        HeatmapHead (kpd_roi_features): image [B,C,H,W], boxes [B,P,4] cxcywh
+        -> [n,64,56,56], the rows ``rows`` (ascending indices into B*P: an
+        int32 device tensor, read in place, or a sequence; None = all) of the
+        forward's own ROI buffer, bit for bit.  No head runs and no host
+        synchronisation happens; indices outside [0, B*P) are the caller's
+        contract (their output rows stay unwritten)."""
+        image = _dev_f32(image, "image")
+        boxes = _dev_f32(boxes, "boxes")
+        if image.dim() != 4:
+            raise ValueError(f"image must be [B, C, H, W], got {tuple(image.shape)}")
+        B, C, H, W = image.shape
+        if boxes.dim() != 3 or boxes.size(0) != B or boxes.size(2) != 4:
+            raise ValueError(f"boxes must be [{B}, P, 4], got {tuple(boxes.shape)}")
+        P = boxes.size(1)
+        rows = _row_list(rows, image.device)
+        n = B * P if rows is None else rows.numel()
+        out = torch.empty(n, 64, 56, 56, device=image.device)
+        if n == 0:   # (an empty tensor has no pointer to tell an empty row list from none)
+            return out
+        with torch.cuda.device(self.device):
+            check(self.lib.kpd_roi_features(self.h, _ptr(image), B, C, H, W, _ptr(boxes), P, _ptr(rows), n, _ptr(out),
+                                            _stream(self.device)), "kpd_roi_features")
+        return out
+
     def debug_buffer(self, name: str) -> torch.Tensor:
         n = ctypes.c_size_t()
         check(self.lib.kpd_debug_copy(self.h, name.encode(), None, 0, ctypes.byref(n), None), "kpd_debug_copy")
@@ -391,6 +421,42 @@ def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
         raise TypeError(f"{name} must be a tensor")
     _require_cuda(t, name)
     return t.float().contiguous()
+
+
+def _row_list(rows, device: torch.device) -> Optional[torch.Tensor]:
+    """A row selection as a contiguous 1-D int32 tensor on ``device`` (None stays None)."""
+    if rows is None:
+        return None
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.tensor([int(r) for r in rows], dtype=torch.int32)
+    if rows.dim() != 1 or rows.is_floating_point():
+        raise ValueError("rows must be a 1-D integer tensor or a sequence of ints")
+    return rows.to(device, torch.int32).contiguous()
+
+
+def roi_targets(keypoints: torch.Tensor, visibilities: torch.Tensor, boxes: torch.Tensor, rows, H: int, W: int,
+                sigma: float):
+    """kpd_roi_targets on keypoints [R,K,2], visibilities [R,K], boxes [R,4]
+    (fp32 device tensors): (heat [n,K,H,W], weight [n,K]) for the ROIs ``rows``
+    (None = all R, in order).  No host synchronisation."""
+    keypoints = _dev_f32(keypoints, "keypoints")
+    visibilities = _dev_f32(visibilities, "visibilities").to(keypoints.device)
+    boxes = _dev_f32(boxes, "boxes").to(keypoints.device)
+    if keypoints.dim() != 3 or keypoints.size(2) != 2:
+        raise ValueError(f"keypoints must be [R, K, 2], got {tuple(keypoints.shape)}")
+    R, K = keypoints.shape[:2]
+    if tuple(visibilities.shape) != (R, K) or tuple(boxes.shape) != (R, 4):
+        raise ValueError(f"visibilities must be [{R}, {K}] and boxes [{R}, 4], got {tuple(visibilities.shape)} "
+                         f"and {tuple(boxes.shape)}")
+    rows = _row_list(rows, keypoints.device)
+    n = R if rows is None else rows.numel()
+    heat = torch.empty(n, K, int(H), int(W), device=keypoints.device)
+    weight = torch.empty(n, K, device=keypoints.device)
+    with torch.cuda.device(keypoints.device):
+        check(load().kpd_roi_targets(_ptr(keypoints), _ptr(visibilities), _ptr(boxes), _ptr(rows), n, R, K, int(H),
+                                     int(W), float(sigma), _ptr(heat), _ptr(weight), _stream(keypoints.device)),
+              "kpd_roi_targets")
+    return heat, weight
 
 
 def decode_heatmaps(heat: torch.Tensor, mode: int, param: float = 0.0):

@@ -2,7 +2,9 @@
 hot path and ``augmentation`` by the device augmentation
 (``dll.data.KeypointAugmentation``); the remaining fields are kept so the
 reference's constructor call ``TrainingConfig()`` and YAML dicts keep working
-(reference: dll/configs/training_config.py:94-133).  No trainer exists."""
+(reference: dll/configs/training_config.py:94-133).  ``dll.training.Trainer``
+reads ``optimizer``, ``lr_scheduler``, ``num_epochs``, ``batch_size`` (through
+``scripts/train.py``), ``checkpoint_interval`` and ``pck_thresholds``."""
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Union
 

@@ -21,8 +21,8 @@ matrices``).  For an image of W x H with centre c = ((W-1)/2, (H-1)/2):
 
 There is no CPU fallback: a CPU tensor raises.  Parity with OpenCV's
 ``warpAffine`` (whose 1/32-pixel grid the image rule follows) is unpinned --
-OpenCV is absent here -- and the effect on accuracy is unmeasured: no trainer
-exists.
+OpenCV is absent here -- and the effect on accuracy is unmeasured: no dataset
+run of ``dll.training.Trainer`` has been made.
 """
 from __future__ import annotations
 

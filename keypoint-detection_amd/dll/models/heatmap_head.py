@@ -242,6 +242,28 @@ def generate_target_heatmap(keypoints: torch.Tensor, heatmap_size: Tuple[int, in
     return out
 
 
+def generate_roi_targets(keypoints: torch.Tensor, visibilities: torch.Tensor, boxes: torch.Tensor, rows=None,
+                         heatmap_size: Tuple[int, int] = (56, 56), sigma: float = 2.0):
+    """Per-ROI training targets of the top-down head (``kpd_roi_targets``,
+    DESIGN.md §3h): keypoints [B,P,K,2] image-normalised, visibilities
+    [B,P,K], boxes [B,P,4] cxcywh -> (heat [n,K,H,W], weight [n,K]) for the
+    ROIs ``rows`` (indices into B*P; None = all, in order).  Each person's own
+    joints are placed in that person's box by the decoders' convention (pixel
+    i is i/(W-1) of the unclamped box) as a Gaussian of peak 1 at the
+    sub-pixel centre; a joint that is unlabelled, outside its box, NaN, or in
+    an empty box gets weight 0 and a zero plane.  On the device, without a
+    host synchronisation."""
+    if keypoints.dim() != 4 or keypoints.size(-1) < 2:
+        raise ValueError(f"keypoints must be [B, P, K, 2], got {tuple(keypoints.shape)}")
+    B, P, K = keypoints.shape[:3]
+    if tuple(visibilities.shape) != (B, P, K) or tuple(boxes.shape) != (B, P, 4):
+        raise ValueError(f"visibilities must be [{B}, {P}, {K}] and boxes [{B}, {P}, 4], got "
+                         f"{tuple(visibilities.shape)} and {tuple(boxes.shape)}")
+    _native._require_cuda(keypoints, "keypoints")
+    return _native.roi_targets(keypoints[..., :2].reshape(B * P, K, 2), visibilities.reshape(B * P, K),
+                               boxes.reshape(B * P, 4), rows, int(heatmap_size[0]), int(heatmap_size[1]), float(sigma))
+
+
 def generate_target_heatmap_adaptive(keypoints: torch.Tensor, heatmap_size: Tuple[int, int],
                                      base_sigma: float = 3.0, adaptive: bool = True) -> torch.Tensor:
     """Reference :226-252: sigma scaled with min(H, W) / 56, floored at 0.8x."""

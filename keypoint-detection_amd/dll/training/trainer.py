@@ -1,0 +1,256 @@
+"""Trainer of the heatmap head on frozen trunk features.
+
+The reference's ``dll.training.Trainer`` signature, checkpoints and history,
+driving the native pieces of a top-down training step:
+
+    rows   = the boxes that are not all zero                 (one host sync)
+    x      = plan.roi_features(image, boxes, rows)            kpd_roi_features, no_grad
+    gt, tw = generate_roi_targets(keypoints, vis, boxes, rows)   kpd_roi_targets
+    loss   = model.loss_fn.heatmap_loss(head(x)[0], gt, tw)   head.train(): native fwd + bwd
+    loss.backward(); optimizer.step()
+
+Only ``model.heatmap_head`` is trained: the optimizer holds its parameters and
+nothing else, the rest of the model stays in eval mode, and every epoch ends
+with a check that no state tensor outside ``heatmap_head.`` changed.  The
+trunk plan is taken from ``model.native_plan(device)`` once per epoch: its
+cache key includes the head's parameters, which change every step, so asking
+per step would re-pack every weight per step; ``roi_features`` never reads the
+(stale) head weights of that plan.
+
+Out of scope: training the trunk, the detector or KEYPOINT_HEAD, AMP
+(``use_amp=True`` raises), multi-GPU training.
+"""
+from __future__ import annotations
+
+import logging
+import time
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple, Union
+
+import torch
+import torch.nn as nn
+from torch.optim import lr_scheduler
+
+from ..configs.training_config import TrainingConfig
+from ..models.heatmap_head import decode_heatmaps, generate_roi_targets
+from ..utils.metric import _metrics_on_device
+
+logger = logging.getLogger(__name__)
+
+HEAD_PREFIX = "heatmap_head."
+TARGET_SIGMA = 2.0   # the reference's _convert_keypoints_to_heatmaps
+
+
+def batch_boxes(batch: Dict) -> torch.Tensor:
+    """The [B, P, 4] box tensor of a collated batch (``efficient_collate_fn`` wraps it in a list)."""
+    bb = batch["bboxes"]
+    bb = bb[0] if isinstance(bb, (list, tuple)) else bb
+    if bb.dim() != 3 or bb.size(-1) != 4:
+        raise ValueError(f"bboxes must be [B, P, 4], got {tuple(bb.shape)}")
+    return bb
+
+
+class Trainer:
+    def __init__(self, model: nn.Module, device: torch.device, train_dataloader, val_dataloader,
+                 config: TrainingConfig, output_dir: Optional[Union[str, Path]] = None, use_amp: bool = False):
+        if use_amp:
+            raise NotImplementedError("AMP training is out of scope: the native train path of the heatmap head is "
+                                      "fp32-accurate (DESIGN.md §3h); construct the Trainer with use_amp=False")
+        if not hasattr(model, "heatmap_head"):
+            raise TypeError("Trainer trains model.heatmap_head; pass a MultiPersonKeypointModel")
+        self.device = torch.device(device)
+        self.model = model.to(self.device)
+        self.head = self.model.heatmap_head
+        self.train_dataloader = train_dataloader
+        self.val_dataloader = val_dataloader
+        self.config = config
+        self.output_dir = Path(output_dir) if output_dir else None
+        if self.output_dir:
+            self.output_dir.mkdir(parents=True, exist_ok=True)
+        self.use_amp = False
+        self.model.eval()
+        self.optimizer = self._create_optimizer()
+        sc = config.lr_scheduler
+        self.scheduler = lr_scheduler.ReduceLROnPlateau(self.optimizer, mode=str(sc.mode), factor=float(sc.factor),
+                                                        patience=int(sc.patience), min_lr=float(sc.min_lr),
+                                                        threshold=float(sc.threshold))
+        self.scheduler_metric = str(sc.metric)
+        self.pck_thresholds = [float(t) for t in config.pck_thresholds]
+        self.history: Dict[str, List] = {}
+        self.epoch = 0               # epochs completed
+        self.best_val_loss = float("inf")
+        self.max_steps: Optional[int] = None   # per epoch (scripts/train.py --max-steps)
+        self._plan = None
+
+    # ------------------------------------------------------------------ setup
+    def _create_optimizer(self) -> torch.optim.Optimizer:
+        oc = self.config.optimizer
+        params = list(self.head.parameters())
+        name = str(oc.name).lower()
+        if name == "adam":
+            return torch.optim.Adam(params, lr=float(oc.learning_rate), betas=(float(oc.beta1), float(oc.beta2)),
+                                    weight_decay=float(oc.weight_decay))
+        if name == "sgd":
+            return torch.optim.SGD(params, lr=float(oc.learning_rate), momentum=float(oc.momentum),
+                                   weight_decay=float(oc.weight_decay))
+        raise ValueError(f"Unsupported optimizer: {oc.name}")
+
+    def _frozen_versions(self) -> Dict[str, Tuple[int, int]]:
+        return {k: (t.data_ptr(), t._version) for k, t in self.model.state_dict(keep_vars=True).items()
+                if not k.startswith(HEAD_PREFIX)}
+
+    def trunk_plan(self):
+        """The model's plan, taken once per epoch (module docstring)."""
+        if self._plan is None:
+            self._plan = self.model.native_plan(self.device)
+        return self._plan
+
+    # ------------------------------------------------------------------ one batch
+    def _features_and_targets(self, batch: Dict):
+        """(x [n,64,56,56], gt [n,K,H,W], tw [n,K], rows [n] int32, boxes [B,P,4]) or None without a
+        labelled box.  The nonzero() below is the step's one host synchronisation."""
+        image = batch["image"].to(self.device)
+        boxes = batch_boxes(batch).to(self.device, torch.float32).contiguous()
+        rows = torch.nonzero((boxes != 0).any(dim=-1).flatten()).flatten().to(torch.int32)   # ascending
+        if rows.numel() == 0:
+            return None
+        with torch.no_grad():
+            x = self.trunk_plan().roi_features(image, boxes, rows)
+        kp = batch["keypoints"].to(self.device, torch.float32)
+        vis = batch["visibilities"].to(self.device, torch.float32)
+        # the head keeps its input's spatial size (config.heatmap_size is unused by it, a reference quirk)
+        gt, tw = generate_roi_targets(kp, vis, boxes, rows, tuple(x.shape[2:]), TARGET_SIGMA)
+        return x, gt, tw, rows, boxes
+
+    def train_step(self, batch: Dict) -> Dict:
+        """One optimizer step on a collated batch: {'loss': 0-d device tensor
+        (detached), 'rows': n, 'skipped': bool}.  A batch without a labelled
+        box is skipped (no step, loss None)."""
+        ft = self._features_and_targets(batch)
+        if ft is None:
+            return {"loss": None, "rows": 0, "skipped": True}
+        x, gt, tw, rows, _ = ft
+        self.head.train()
+        self.optimizer.zero_grad(set_to_none=True)
+        heat = self.head(x)[0]
+        loss = self.model.loss_fn.heatmap_loss(heat, gt, tw)
+        loss.backward()
+        self.optimizer.step()
+        return {"loss": loss.detach(), "rows": int(rows.numel()), "skipped": False}
+
+    def train_epoch(self) -> Dict[str, float]:
+        self._plan = None
+        self.model.eval()
+        before = self._frozen_versions()
+        losses, steps, skipped = [], 0, 0
+        for batch in self.train_dataloader:
+            if self.max_steps is not None and steps + skipped >= self.max_steps:
+                break
+            out = self.train_step(batch)
+            if out["skipped"]:
+                skipped += 1
+                continue
+            steps += 1
+            losses.append(out["loss"])
+        self.head.eval()
+        changed = [k for k, v in self._frozen_versions().items() if before.get(k) != v]
+        assert not changed, f"state outside {HEAD_PREFIX} changed during the epoch: {changed[:5]}"
+        loss = float(torch.stack(losses).double().mean()) if losses else 0.0
+        return {"loss": loss, "steps": steps, "skipped_steps": skipped}
+
+    def validate_epoch(self) -> Dict[str, float]:
+        """Mean loss, ADE and PCK over the validation batches with a labelled
+        box: the head in eval mode through its own plan on the same features
+        and targets; the heatmaps argmax-decoded and mapped to image
+        coordinates through the unclamped box, against the labelled joints."""
+        self._plan = None
+        self.model.eval()
+        names = ["loss", "avg_ADE"] + [f"pck_{t}" for t in self.config.pck_thresholds]
+        sums, n = dict.fromkeys(names, 0.0), 0
+        with torch.no_grad():
+            for batch in self.val_dataloader:
+                if self.max_steps is not None and n >= self.max_steps:
+                    break
+                ft = self._features_and_targets(batch)
+                if ft is None:
+                    continue
+                x, gt, tw, rows, boxes = ft
+                heat = self.head(x)[0]
+                loss = self.model.loss_fn.heatmap_loss(heat, gt, tw)
+                kp_roi, _ = decode_heatmaps(heat)                                   # [n, K, 2] in the ROI's frame
+                b = boxes.view(-1, 4)[rows.long()].unsqueeze(1)                     # [n, 1, 4]
+                pred = kp_roi * b[..., 2:] + (b[..., :2] - b[..., 2:] / 2)           # unclamped box
+                K = heat.size(1)
+                want = batch["keypoints"].to(self.device, torch.float32).reshape(-1, K, 2)[rows.long()]
+                vis = batch["visibilities"].to(self.device, torch.float32).reshape(-1, K)[rows.long()]
+                vals = _metrics_on_device(pred, want, vis, self.pck_thresholds)
+                for name, v in zip(names, [float(loss)] + vals):
+                    sums[name] += float(v)
+                n += 1
+        return {k: v / max(n, 1) for k, v in sums.items()}
+
+    # ------------------------------------------------------------------ checkpoints
+    def _checkpoint(self, epoch: int) -> Dict:
+        return {"epoch": int(epoch), "model_state_dict": self.model.state_dict(),
+                "optimizer_state_dict": self.optimizer.state_dict(),
+                "history": {k: list(v) for k, v in self.history.items()}}
+
+    def save_checkpoint(self, epoch: int, is_best: bool = False, periodic: bool = True) -> None:
+        if not self.output_dir:
+            return
+        ckpt = self._checkpoint(epoch)
+        if periodic:
+            torch.save(ckpt, self.output_dir / f"checkpoint_epoch_{epoch}.pth")
+        if is_best:
+            torch.save(ckpt, self.output_dir / "best_model.pth")
+
+    def resume(self, path: Union[str, Path]) -> int:
+        """Restore the model, the optimizer, the epoch and the history; returns the epochs completed."""
+        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        self.model.load_state_dict(ckpt["model_state_dict"])
+        self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        self.history = {k: list(v) for k, v in ckpt.get("history", {}).items()}
+        self.epoch = int(ckpt["epoch"])
+        if self.history.get("loss"):
+            self.best_val_loss = min(self.history["loss"])
+        self._plan = None
+        return self.epoch
+
+    # ------------------------------------------------------------------ loop
+    def _scheduler_value(self, val: Dict[str, float]) -> float:
+        return float(val.get(self.scheduler_metric, val["loss"]))
+
+    def _record(self, epoch: int, train: Dict[str, float], val: Dict[str, float], lr: float, seconds: float) -> Dict:
+        line = {"epoch": int(epoch), "train_loss": float(train["loss"]), "loss": float(val["loss"]),
+                "avg_ADE": float(val["avg_ADE"])}
+        line.update({k: float(v) for k, v in val.items() if k.startswith("pck_")})
+        line.update({"learning_rate": float(lr), "steps": int(train["steps"]),
+                     "skipped_steps": int(train["skipped_steps"]), "seconds": float(seconds)})
+        for k, v in line.items():
+            self.history.setdefault(k, []).append(v)
+        return line
+
+    def train(self, on_epoch=None) -> Tuple[nn.Module, Dict]:
+        """Epochs ``self.epoch + 1 .. config.num_epochs``; ``on_epoch(line)``
+        receives each epoch's record (plain Python numbers).  Returns the model
+        and the history."""
+        for epoch in range(self.epoch + 1, int(self.config.num_epochs) + 1):
+            t0 = time.perf_counter()
+            train = self.train_epoch()
+            val = self.validate_epoch()
+            self.scheduler.step(self._scheduler_value(val))
+            lr = self.optimizer.param_groups[0]["lr"]
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
+            line = self._record(epoch, train, val, lr, time.perf_counter() - t0)
+            self.epoch = epoch
+            is_best = val["loss"] < self.best_val_loss
+            if is_best:
+                self.best_val_loss = val["loss"]
+            interval = max(1, int(self.config.checkpoint_interval))
+            self.save_checkpoint(epoch, is_best=is_best, periodic=epoch % interval == 0)
+            logger.info("epoch %d: train loss %.6f  val loss %.6f  ADE %.5f  lr %.2e", epoch, train["loss"],
+                        val["loss"], val["avg_ADE"], lr)
+            if on_epoch is not None:
+                on_epoch(line)
+        return self.model, self.history

@@ -1,0 +1,189 @@
+#!/usr/bin/env python3
+"""Cost of one heatmap-head training step and of its two new device pieces,
+alternated in one process.
+
+64 seeded 256 x 192 images with 2 persons each (128 ROIs):
+
+(a) `Plan.roi_features` (kpd_roi_features: the fused forward's trunk stages +
+    one gathering transpose) against
+      * the piecewise composition `Plan.backbone` ->
+        `ChannelAttention.native_select(select=True)` -> `_native.roi_align`
+        (all four FPN levels, the whole level 0), and
+      * the full eval forward of the same batch (`model(batch)`), of which it
+        is a prefix plus one transpose.
+(b) `generate_roi_targets` (kpd_roi_targets) against the equivalent
+    broadcasting torch chain and a device-to-device `copy_` of the output's
+    bytes (the kernel's only traffic is that output, written once).
+(c) One whole `Trainer.train_step` (Adam) and its split: trunk, targets, head
+    step (forward + loss + backward), optimizer step.
+
+Every variant is timed with HIP events around `--inner` back-to-back calls on
+resident tensors; after warm-ups the variants alternate `--rounds` times and
+the medians are reported.  One JSON line; the tool sets no pass/fail threshold.
+
+The measurement runs in a child process under its own `timeout`:
+
+    python tools/bench_train_step.py [--images 64] [--rounds 7] [--inner 3] [--timeout 600]
+"""
+import argparse
+import json
+import statistics
+import subprocess
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+
+
+def worker(a):
+    sys.path.insert(0, str(ROOT / "keypoint-detection_amd"))
+    import torch
+    from dll import _native
+    from dll.configs import ModelConfig, TrainingConfig
+    from dll.models import MultiPersonKeypointModel
+    from dll.models.heatmap_head import generate_roi_targets
+    from dll.models.synthetic import synthetic_boxes, synthetic_images, synthetic_state_dict
+    from dll.training import Trainer
+    dev = torch.device("cuda", 0)
+    B, P, K = a.images, 2, 17
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def alternate(variants, inner):
+        for _ in range(2):
+            for fn in variants.values():
+                timed(fn, inner)
+        ms = {k: [] for k in variants}
+        for _ in range(a.rounds):
+            for k, fn in variants.items():
+                ms[k].append(timed(fn, inner))
+        return {k: statistics.median(v) for k, v in ms.items()}, ms
+
+    def report(med, ms, names):
+        out = {}
+        for k in names:
+            out[k + "_ms"] = round(med[k], 4)
+            out[k + "_ms_min_max"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+        return out
+
+    cfg = TrainingConfig()
+    model = MultiPersonKeypointModel(ModelConfig(), cfg)
+    model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=0))
+    trainer = Trainer(model, dev, [], [], cfg)
+    image = synthetic_images(B, 3, 256, 192, seed=a.seed + 1, device=dev)
+    boxes = synthetic_boxes(B, P, seed=a.seed + 2, device=dev)
+    g = torch.Generator().manual_seed(a.seed + 3)
+    uv = (torch.rand(B, P, K, 2, generator=g) * 0.9 + 0.05).to(dev)
+    kp = boxes[:, :, None, :2] - boxes[:, :, None, 2:] / 2 + uv * boxes[:, :, None, 2:]
+    vis = torch.randint(0, 3, (B, P, K), generator=g).float().to(dev)
+    batch = {"image": image, "bboxes": [boxes], "keypoints": kp, "visibilities": vis}
+    rows = torch.arange(B * P, dtype=torch.int32, device=dev)
+    plan = model.native_plan(dev)
+    res = {"metric": "train_step_ms", "images": B, "persons": P, "rounds": a.rounds, "inner": a.inner}
+
+    # ---- (a) the trunk's ROI features
+    bidx = torch.arange(B, device=dev, dtype=torch.float32).repeat_interleave(P)
+
+    def fused():
+        return plan.roi_features(image, boxes, rows)
+
+    def piecewise():
+        level0 = plan.backbone(image)[0]
+        sel = model.channel_attention.native_select(level0, 64, select=True)[2]
+        Hf, Wf = sel.shape[2:]
+        b = boxes.view(-1, 4)
+        x1, y1 = (b[:, 0] - b[:, 2] / 2).clamp(0, 1) * Wf, (b[:, 1] - b[:, 3] / 2).clamp(0, 1) * Hf
+        x2, y2 = (b[:, 0] + b[:, 2] / 2).clamp(0, 1) * Wf, (b[:, 1] + b[:, 3] / 2).clamp(0, 1) * Hf
+        return _native.roi_align(sel, torch.stack([bidx, x1, y1, x2, y2], 1), (56, 56))
+
+    def forward():
+        with torch.no_grad():
+            return model({"image": image, "bboxes": boxes})
+
+    xf, xp = fused(), piecewise()
+    torch.cuda.synchronize()
+    res["roi_features_max_abs_diff_to_piecewise"] = float((xf - xp).abs().max())
+    del xp
+    med, ms = alternate({"roi_features": fused, "piecewise": piecewise, "eval_forward": forward}, a.inner)
+    res["trunk"] = report(med, ms, ("roi_features", "piecewise", "eval_forward"))
+    res["trunk"]["roi_features_over_piecewise"] = round(med["roi_features"] / med["piecewise"], 3)
+    res["trunk"]["roi_features_over_eval_forward"] = round(med["roi_features"] / med["eval_forward"], 3)
+    torch.cuda.empty_cache()
+
+    # ---- (b) the targets
+    H = W = 56
+    sigma = 2.0
+    xs = torch.arange(W, device=dev, dtype=torch.float32).view(1, 1, 1, W)
+    ys = torch.arange(H, device=dev, dtype=torch.float32).view(1, 1, H, 1)
+
+    def native_targets():
+        return generate_roi_targets(kp, vis, boxes, rows, (H, W), sigma)
+
+    def chain_targets():
+        b = boxes.view(-1, 1, 4)
+        k, v = kp.view(-1, K, 2), vis.view(-1, K)
+        u = (k[..., 0] - (b[..., 0] - b[..., 2] / 2)) / b[..., 2]
+        w = (k[..., 1] - (b[..., 1] - b[..., 3] / 2)) / b[..., 3]
+        on = (b[..., 2] > 0) & (b[..., 3] > 0) & (v > 0) & (u >= 0) & (u <= 1) & (w >= 0) & (w <= 1)
+        px, py = (u * (W - 1))[..., None, None], (w * (H - 1))[..., None, None]
+        heat = torch.exp(-((xs - px) ** 2 + (ys - py) ** 2) / (2 * sigma * sigma))
+        return torch.where(on[..., None, None], heat, torch.zeros((), device=dev)), on.float()
+
+    hn, wn = native_targets()
+    hc, wc = chain_targets()
+    torch.cuda.synchronize()
+    res["targets_check"] = {"weights_equal": bool(torch.equal(wn, wc)), "max_abs_diff": float((hn - hc).abs().max())}
+    ca, cb = torch.empty_like(hn), torch.empty_like(hn)
+    del hc
+    med, ms = alternate({"native": native_targets, "chain": chain_targets, "copy": lambda: cb.copy_(ca)}, a.inner)
+    res["targets"] = report(med, ms, ("native", "chain", "copy"))
+    res["targets"]["native_over_chain"] = round(med["native"] / med["chain"], 3)
+    res["targets"]["native_over_copy"] = round(med["native"] / med["copy"], 3)
+    res["targets"]["output_mbytes"] = round(hn.numel() * 4 / 1e6, 2)
+    del ca, cb
+    torch.cuda.empty_cache()
+
+    # ---- (c) the step and its split
+    head, opt, crit = trainer.head, trainer.optimizer, model.loss_fn.heatmap_loss
+    gt, tw = hn, wn
+    head.train()
+
+    def head_step():
+        opt.zero_grad(set_to_none=True)
+        crit(head(xf)[0], gt, tw).backward()
+
+    head_step()   # gradients exist for the optimizer-only variant
+    med, ms = alternate({"train_step": lambda: trainer.train_step(batch), "trunk": fused, "targets": native_targets,
+                         "head_step": head_step, "optimizer": opt.step}, max(1, a.inner // 2))
+    res["step"] = report(med, ms, ("train_step", "trunk", "targets", "head_step", "optimizer"))
+    res["step"]["rois"] = B * P
+    print(json.dumps(res))
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=3, help="back-to-back calls per timed interval")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--timeout", type=int, default=600, help="seconds the measuring child may take")
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.worker:
+        return worker(a)
+    # the GPU step: a fresh child under its own time limit
+    cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, str(Path(__file__).resolve()), "--worker"]
+    cmd += [v for v in sys.argv[1:] if v != "--worker"]
+    return subprocess.run(cmd).returncode
+
+
+if __name__ == "__main__":
+    sys.exit(main())
