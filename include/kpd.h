@@ -159,8 +159,11 @@ int kpd_nms(const float* boxes, const float* scores, int n, float iou_threshold,
  * pipeline's edge blend (to_grayscale_clahe :55-73: blur, median, Canny,
  * morphology, addWeighted; single plane only), Gaussian 3x3 sigma 0.5 (RGB
  * pipeline, :105), PIL-exact bilinear resize, ToTensor + Normalize(mean, std)
- * (host arrays of C' floats).  Stream-ordered scratch (hipMallocAsync).
- * Replaces ITransform.__call__ (transforms.py:110-113). */
+ * (host arrays of C' floats).  Replaces ITransform.__call__
+ * (transforms.py:110-113).  This is kpd_preprocess_batch (below) with n = 1:
+ * the same code, so the same checks (a failure's message begins
+ * "kpd_preprocess:"), one stream-ordered scratch allocation, a pitched image
+ * read in place, no synchronisation. */
 #define KPD_PRE_GRAY 1
 #define KPD_PRE_CLAHE 2
 #define KPD_PRE_BLUR 4
@@ -176,8 +179,9 @@ int kpd_preprocess(const uint8_t* src, int height, int width, int channels, int 
  * pitch in bytes (any pitch >= width * channels: a strided view needs no
  * dense copy).  flags, CLAHE parameters, output size, mean and std are shared.
  * dst: fp32 [n][C'][out_h][out_w], contiguous (device) -- the forward's input.
- * Image i of dst is bit for bit what kpd_preprocess writes for image i alone:
- * every stage is integer or contraction-free arithmetic.
+ * kpd_preprocess runs this code with n = 1, and an image's result does not
+ * depend on the images it is batched with: every stage is integer or
+ * contraction-free arithmetic within one image.
  *
  * Every stage takes the image index in its grid and reads the image's
  * geometry from a descriptor table that travels by value in the kernel
@@ -188,10 +192,12 @@ int kpd_preprocess(const uint8_t* src, int height, int width, int channels, int 
  * one workgroup each; the chain behind it (dilate, erode, dilate, erode,
  * Gaussian 3x3, maximum) is one LDS-tiled kernel.
  *
- * Arguments are checked before any device work: the checks of
- * kpd_preprocess per image (the downscale-factor limit of 31 included), n > 0
- * and non-null arrays; a failure is KPD_EINVAL and its message names the
- * first offending image ("image <i>: ...").  Scratch is one stream-ordered
+ * Arguments are checked before any device work: non-null pointers, n > 0,
+ * channels 1 or 3, positive sizes, GRAY only on 3 channels, EDGES only on a
+ * single-plane pipeline, and per image pitch >= width * channels, a CLAHE
+ * tile grid within the image and a downscale factor of at most 31; a failure
+ * is KPD_EINVAL and its message names the first offending image
+ * ("image <i>: ...").  Scratch is one stream-ordered
  * allocation per call (hipMallocAsync, freed on the stream), carved by prefix
  * sums over the images with 64-bit offsets.  The call does not synchronise
  * and reads none of the host arrays after it returns. */

@@ -7,6 +7,8 @@ same fp32 ops as torchvision); CLAHE, gray conversion, blurs and the grayscale
 edge blend (median, Canny, morphology, addWeighted) bit-exact vs the oracle
 restatement (parity unpinned vs OpenCV, which is absent).
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -103,8 +105,96 @@ def test_itransform_api_importable():
     assert t.size == (64, 64) and t.grayscale is False
 
 
+def _entry(src, H, W, C, pitch, flags, out_size, mean, std, dst, tiles=(8, 8), stream=None):
+    """lib.kpd_preprocess itself (preprocess() always hands it a dense image with pitch = W * C);
+    src / dst are addresses, mean / std sequences or None."""
+    from dll import _native
+    lib = _native.load()
+    m = None if mean is None else (ctypes.c_float * 3)(*mean, *([0.0] * (3 - len(mean))))
+    s = None if std is None else (ctypes.c_float * 3)(*std, *([1.0] * (3 - len(std))))
+    rc = lib.kpd_preprocess(ctypes.c_void_p(src), H, W, C, pitch, flags, ctypes.c_float(2.0), tiles[0], tiles[1],
+                            out_size[0], out_size[1], m, s, ctypes.c_void_p(dst), ctypes.c_void_p(stream))
+    return rc, lib.kpd_last_error().decode()
+
+
+def test_entry_argument_checks_before_device_work():
+    """kpd_preprocess on made-up addresses: only the argument checks may run.  Every rejected input
+    answers KPD_EINVAL with a message that names the entry that was called, not the batched one's image 0."""
+    GRAY, CLAHE, EDGES = 1, 2, 8
+    ok = dict(src=0x10000, H=40, W=50, C=3, pitch=150, flags=GRAY | CLAHE | EDGES, out_size=(32, 32),
+              mean=(0.5,), std=(0.5,), dst=0x900000)
+    bad = {"null src": dict(src=None), "null dst": dict(dst=None), "null mean": dict(mean=None),
+           "null std": dict(std=None),
+           "H = 0": dict(H=0), "W < 0": dict(W=-3), "out_h = 0": dict(out_size=(0, 32)),
+           "out_w < 0": dict(out_size=(32, -1)),
+           "C = 2": dict(C=2, pitch=100, flags=0), "C = 4": dict(C=4, pitch=200, flags=0),
+           "pitch < W * C": dict(pitch=149),
+           "GRAY on one plane": dict(C=1, pitch=50, flags=GRAY),
+           "EDGES on three planes": dict(flags=CLAHE | EDGES),
+           "tiles_x = 0": dict(tiles=(0, 8)), "tiles_y < 0": dict(tiles=(8, -1)),
+           "tiles_x > W": dict(W=7, pitch=21), "tiles_y > H": dict(H=7),
+           "downscale 40 in y": dict(H=32 * 40, flags=GRAY),
+           "downscale 32 in x": dict(W=32 * 32, pitch=3 * 1024, flags=0)}
+    for name, change in bad.items():
+        rc, msg = _entry(**{**ok, **change})
+        assert rc == -1, name
+        assert msg.startswith("kpd_preprocess:") and "image 0" not in msg, (name, msg)
+
+
 gpu = pytest.mark.gpu
 DEV = torch.device("cuda:0")
+
+
+def _run_entry(view, flags, out_size, mean, std):
+    """kpd_preprocess on a device view whose rows are dense (last strides (C, 1)), read at its row pitch."""
+    v = view if view.dim() == 3 else view[:, :, None]
+    H, W, C = v.shape
+    assert v.stride(2) == 1 and v.stride(1) == C
+    out = torch.empty(1 if flags & 1 else C, *out_size, device=DEV, dtype=torch.float32)
+    with torch.cuda.device(DEV):
+        rc, msg = _entry(v.data_ptr(), H, W, C, v.stride(0), flags, out_size, mean, std, out.data_ptr(),
+                         stream=torch.cuda.current_stream(DEV).cuda_stream)
+    assert rc == 0, msg
+    return out.cpu().numpy()
+
+
+@gpu
+def test_gpu_entry_reads_pitched_input_in_place():
+    """pitch > W * C through the C entry: a column slice of a wider tensor whose padding holds a value the
+    image lacks.  Identity, vertical-only and horizontal-only resizes (the first two read the source in the
+    vertical pass), the RGB pipeline, and the edge blend on a single plane; all bit for bit the oracle on
+    the dense image."""
+    from dll.data.transforms import FLAG_BLUR, FLAG_CLAHE, FLAG_EDGES, IMAGENET_MEAN, IMAGENET_STD
+    PAD = 201
+    rng = np.random.default_rng(31)
+    img = _edge_image(rng, 33, 47)
+    img[img == PAD] = PAD - 1
+    wide = torch.full((33, 60, 3), PAD, dtype=torch.uint8, device=DEV)
+    wide[:, 6:53] = torch.from_numpy(img).to(DEV)
+    view = wide[:, 6:53]
+    assert view.stride(0) == 180 and not (img == PAD).any()
+    for size in ((33, 47), (20, 47), (33, 30)):
+        got = _run_entry(view, 0, size, IMAGENET_MEAN, IMAGENET_STD)
+        want = O.to_tensor_normalize(O.pil_resize_bilinear(img, *size), IMAGENET_MEAN, IMAGENET_STD)
+        assert np.array_equal(got, want), size
+    got = _run_entry(view, FLAG_CLAHE | FLAG_BLUR, (32, 32), IMAGENET_MEAN, IMAGENET_STD)
+    assert np.array_equal(got, O.itransform_rgb(img, 32, 2.0, (8, 8)))
+    plane = np.ascontiguousarray(_edge_image(rng, 40, 50)[..., 1])
+    plane[plane == PAD] = PAD - 1
+    wide = torch.full((40, 57), PAD, dtype=torch.uint8, device=DEV)
+    wide[:, 4:54] = torch.from_numpy(plane).to(DEV)
+    got = _run_entry(wide[:, 4:54], FLAG_EDGES, (24, 24), (0.0,), (1.0,))
+    want = O.to_tensor_normalize(O.pil_resize_bilinear(O.edge_blend_u8(plane), 24, 24), [0.0], [1.0])
+    assert np.array_equal(got, want)
+
+
+@gpu
+def test_gpu_gray_alone_vs_oracle():
+    """GRAY without CLAHE or EDGES: the resize reads the gray plane straight from the conversion."""
+    from dll.data.transforms import FLAG_GRAY, preprocess
+    img = _edge_image(np.random.default_rng(37), 24, 20)
+    got = preprocess(torch.from_numpy(img).to(DEV), (24, 20), [0.5], [0.5], FLAG_GRAY).cpu().numpy()
+    assert np.array_equal(got, O.to_tensor_normalize(O.rgb_to_gray_cv(img), [0.5], [0.5]))
 
 
 @gpu

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Rate of the preprocessing stage in front of the forward: n single
-`preprocess` calls (kpd_preprocess, one image per call) against one
-`preprocess_batch` (kpd_preprocess_batch) over the same images, in one process.
+"""Rate of the preprocessing stage in front of the forward, and the overhead
+of calling it per image: n single `preprocess` calls (kpd_preprocess, the
+batched pipeline at n = 1: one allocation and one set of launches per image)
+against one `preprocess_batch` (kpd_preprocess_batch) over the same images, in
+one process.  Both run the same kernels, so the ratio is what batching saves
+in launches, allocations and serialised Canny floods.
 
 Workload: 64 seeded uint8 images of 480 x 640 x 3 (blobs, bars and steps over
 mild noise -- photo-like edge density, not white noise), the grayscale
 pipeline of scripts/predict.py (gray -> CLAHE 2.0 / 8x8 -> edge blend) to
 256 x 192.  After warm-ups of both paths and a bit-equality check of their
-outputs, the two are timed alternately (HIP events around the whole set of
+outputs (a check of the n = 1 wrapper), the two are timed alternately (HIP events around the whole set of
 calls, `--rounds` times each; the median is reported).  One JSON line:
 images/s of both paths, their ratio, and the C2 forward rate recorded in
 BENCH_r06.json for scale.
