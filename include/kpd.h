@@ -700,6 +700,20 @@ int kpd_conv3x3_forward(const float* x, const float* w, const float* b, int N, i
                         void* stream);
 int kpd_conv3x3_backward(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
                          float* gx, float* gw, float* gb, void* stream);
+/* The same two calls with the arithmetic chosen by `precision`:
+ *   KPD_PRECISION_SPLIT: the calls above, bit for bit.
+ *   KPD_PRECISION_MIXED: bf16 mixed precision for training.
+ *     Every product of the forward, the dgrad and the wgrad is the product of
+ *     its two operands each rounded to bf16 (nearest even) from its fp32
+ *     value, accumulated in fp32: one v_mfma_f32_16x16x32_bf16 per MAC group
+ *     instead of three f16 products, and no scale passes.  The bias is added
+ *     in fp32; gb is the sum of the unrounded gy (the split path's kernels and
+ *     bits).  Tensors stay NCHW fp32; fixed-order sums, deterministic.
+ * Any other value: KPD_EINVAL. */
+int kpd_conv3x3_forward_prec(const float* x, const float* w, const float* b, int N, int C, int H, int W, int O,
+                             float* y, int precision, void* stream);
+int kpd_conv3x3_backward_prec(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
+                              float* gx, float* gw, float* gb, int precision, void* stream);
 
 /* Training side: nn.BatchNorm2d in train mode (batch statistics) fused with
  * the ReLU and the Dropout2d that follow it in the heatmap head's

@@ -19,6 +19,11 @@
 // steps of 16 staged through LDS, four waves of 2 x 2 fragments.  wgrad sums
 // fixed K slices in slice order and the bias sums run in fixed orders: every
 // result is deterministic.
+// Precision "mixed" (kpd_conv3x3_*_prec): the same three on
+// operands rounded to bf16 from their fp32 values, one bf16 MFMA product per
+// MAC, fp32 accumulation, no scales -- the non-split hmconv kernel in its
+// linear mode, the per-tap GEMM on bf16 planes, and the generic kernel with its
+// operands rounded as it loads them; the bias and its gradient stay fp32.
 #include <algorithm>
 
 #include "kpd_common.h"
@@ -30,6 +35,9 @@ constexpr int TB = 64, TK = 16;
 
 enum { C3_FWD = 0, C3_DGRAD = 1, C3_WGRAD = 2 };
 
+// v rounded to bf16 (nearest even), as fp32
+__device__ __forceinline__ float bf16_round(float v) { return (float)(__bf16)v; }
+
 // map offset of pixel p shifted by tap t (sign +1: p + d(t), -1: p - d(t)); -1 outside
 __device__ __forceinline__ int shift_px(int p, int t, int sgn, int H, int W) {
   const int y = p / W, x = p - y * W;
@@ -40,7 +48,10 @@ __device__ __forceinline__ int shift_px(int p, int t, int sgn, int H, int W) {
 // MODE C3_FWD:   M = O, N = HW, K = 9C, per image (blockIdx.z)
 // MODE C3_DGRAD: M = C, N = HW, K = 9O, per image
 // MODE C3_WGRAD: M = O, N = 9C, K = NI*HW, K slice blockIdx.z of length kslice
-template <int MODE>
+// BF: both operands rounded to bf16 (nearest even) as they are loaded -- the
+// products are then those of precision "mixed" (DESIGN.md §3i), still exact
+// in the fp32 MFMA
+template <int MODE, bool BF = false>
 __global__ __launch_bounds__(256) void conv3_gemm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ gy, const float* __restrict__ bias,
                                                          int C, int H, int W, int O, int kslice, int ktot,
@@ -101,6 +112,10 @@ __global__ __launch_bounds__(256) void conv3_gemm_kernel(const float* __restrict
       // B: forward / dgrad contiguous along n (pixels), wgrad along k (pixels)
       if constexpr (MODE == C3_WGRAD) rb[u] = ldB(k0 + e % TK, n0 + e / TK);
       else rb[u] = ldB(k0 + e / TB, n0 + e % TB);
+      if constexpr (BF) {
+        ra[u] = bf16_round(ra[u]);
+        rb[u] = bf16_round(rb[u]);
+      }
     }
   };
   auto stash = [&]() {
@@ -597,6 +612,167 @@ __global__ __launch_bounds__(64 * NWM * NWN) void k6_wgrad_split_kernel(const fl
       }
 }
 
+// ---- precision "mixed" (DESIGN.md §3i): bf16 operands, one product per MAC, no scales
+// x [N][C][56][56] fp32 -> the hmconv layout [N * 3249][C] bf16 (round to
+// nearest even of the fp32 value, unscaled) at interior positions (borders
+// zeroed by the caller: k6_hm_border_kernel with C / 2, i.e. 2 bytes a channel)
+__global__ __launch_bounds__(256) void k6_to_hm_bf_kernel(const float* __restrict__ x, int C,
+                                                          __bf16* __restrict__ out) {
+  __shared__ float t[32][65];
+  const int n = blockIdx.z, cg = blockIdx.y, p0 = blockIdx.x * 64, tid = threadIdx.x;
+  const float* src = x + ((size_t)n * C + cg * 32) * (kHmSide * kHmSide);
+  for (int i = tid; i < 32 * 64; i += 256) {
+    const int c = i >> 6, pp = i & 63;
+    t[c][pp] = p0 + pp < kHmSide * kHmSide ? src[(size_t)c * (kHmSide * kHmSide) + p0 + pp] : 0.f;
+  }
+  __syncthreads();
+  const int pp = tid >> 2, c8 = (tid & 3) * 8, p = p0 + pp;
+  if (p >= kHmSide * kHmSide) return;
+  const int y = p / kHmSide, xx = p - y * kHmSide;
+  bf16x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (__bf16)t[c8 + e][pp];
+  *reinterpret_cast<bf16x8*>(out + ((size_t)n * kHmRoiPos + (y + 1) * kHmPitch + xx) * C + cg * 32 + c8) = v;
+}
+
+// w [O][C][3][3] -> bf16 weights [co'][9][ci'] (hmconv_kernel's non-split
+// layout), rows co' >= cout zero up to cout_p; flip and the odd rows' sign as
+// k6_pack_w_kernel (bf16(-v) = -bf16(v): the products are unchanged, and
+// k6_bias_sign_kernel / k6_nhwc_nchw_kernel are shared with the split path)
+__global__ __launch_bounds__(256) void k6_pack_w_bf_kernel(const float* __restrict__ w, int O, int C, int flip,
+                                                           int cout_p, __bf16* __restrict__ ws) {
+  const int cin = flip ? O : C, cout = flip ? C : O;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)cout_p * 9 * cin) return;
+  const int ci = (int)(i % cin);
+  const long r = i / cin;
+  const int t = (int)(r % 9), co = (int)(r / 9);
+  const float v = co >= cout ? 0.f : flip ? w[((size_t)ci * C + co) * 9 + (8 - t)] : w[((size_t)co * C + ci) * 9 + t];
+  ws[i] = (__bf16)((co & 1) ? -v : v);
+}
+
+// k6_plane_kernel for precision "mixed": the planes rounded to bf16 (nearest
+// even, from the fp32 value), the plane's sum psum[n][ch] (psum non-null) of
+// the unrounded values in k6_plane_kernel's order -- the same bias gradient bits
+__global__ __launch_bounds__(256) void k6_plane_bf_kernel(const float* __restrict__ in, int Ch, int H, int W, int Chp,
+                                                          int Qs, __bf16* __restrict__ out, float* __restrict__ psum) {
+  __shared__ float red[256];
+  const int ch = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, W2 = W + 2;
+  const bool live = ch < Ch;
+  const float* src = in + ((size_t)n * Ch + (live ? ch : 0)) * H * W;
+  __bf16* dst = out + ((size_t)n * Chp + ch) * Qs;
+  float sum = 0.f;
+  for (int q = tid; q < Qs; q += 256) {
+    const int yy = q / W2 - 1, xx = q - (yy + 1) * W2 - 1;
+    float v = 0.f;
+    if (live && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+      v = src[yy * W + xx];
+      sum += v;
+    }
+    dst[q] = (__bf16)v;
+  }
+  if (psum && live) {
+    red[tid] = sum;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if (tid < h) red[tid] += red[tid + h];
+      __syncthreads();
+    }
+    if (tid == 0) psum[(size_t)n * Ch + ch] = red[0];
+  }
+}
+
+// wgrad partials on bf16 products: k6_wgrad_split_kernel's GEMM (same tiles,
+// K-steps of 32 positions, same slice partials) on bf16 planes
+// (k6_plane_bf_kernel), one v_mfma_f32_16x16x32_bf16 per fragment pair, no
+// scales.  A thread stages 4 positions (8 bytes) of a row per K-step: gy
+// aligned; x shifted by the tap's offset, so it loads the two aligned 8-byte
+// pieces around its 4 elements and funnel-shifts them by the (block-uniform)
+// misalignment sh = off mod 4 (xP's guard covers the 3 elements below and 4
+// above).  An LDS row = 32 bf16 + 16 B pad (80 B: the 16 rows of a b128
+// fragment read start 20 banks apart and cover the 64 banks once).
+constexpr int kWbRow = 80;
+template <int NWM, int NWN, int FJ>
+__global__ __launch_bounds__(64 * NWM * NWN) void k6_wgrad_bf_kernel(const __bf16* __restrict__ gyP,
+                                                                     const __bf16* __restrict__ xP, int N, int Op,
+                                                                     int Cp, int O, int C, int W2, int Qs, int ips,
+                                                                     float* __restrict__ part) {
+  constexpr int NT = 64 * NWM * NWN, TM = 64 * NWM, TN = 16 * FJ * NWN, RP = NT / 8, UA = TM / RP, UBn = TN / RP;
+  __shared__ __attribute__((aligned(16))) char As[2][TM * kWbRow];
+  __shared__ __attribute__((aligned(16))) char Bs[2][TN * kWbRow];
+  const int c0 = blockIdx.x * TN, o0 = blockIdx.y * TM, t = blockIdx.z % 9, s = blockIdx.z / 9;
+  const int off = (t / 3 - 1) * W2 + (t % 3 - 1);
+  const int sh = off & 3, sbits = sh * 16;   // elements of misalignment of the shifted x reads (two's complement: mod 4)
+  const int n0 = s * ips, n1 = min(N, n0 + ips);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / NWN, wn = wave % NWN;
+  const int g = lane >> 4, r16 = lane & 15;
+  const int lrow = tid >> 3, lq = (tid & 7) * 4;   // loader: rows lrow + RP u; positions lq .. lq + 3
+  f32x4 acc[4][FJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int total = (n1 - n0) * (Qs / kWsK);
+  const __bf16* pa = gyP + ((size_t)n0 * Op + o0 + lrow) * Qs + lq;
+  const __bf16* pb = xP + ((long)((size_t)n0 * Cp + c0 + lrow) * Qs + lq + (off - sh));   // 8-byte aligned
+  const size_t r32 = (size_t)RP * Qs, ajump = (size_t)(Op - 1) * Qs, bjump = (size_t)(Cp - 1) * Qs;
+  int fq = 0;
+  typedef unsigned long long u64;
+  u64 ra[UA], rb0[UBn], rb1[UBn];
+  auto fetch = [&]() {
+#pragma unroll
+    for (int u = 0; u < UA; ++u) ra[u] = *reinterpret_cast<const u64*>(pa + u * r32);
+#pragma unroll
+    for (int u = 0; u < UBn; ++u) {
+      rb0[u] = *reinterpret_cast<const u64*>(pb + u * r32);
+      rb1[u] = *reinterpret_cast<const u64*>(pb + u * r32 + 4);
+    }
+    pa += kWsK;
+    pb += kWsK;
+    if ((fq += kWsK) == Qs) { fq = 0; pa += ajump; pb += bjump; }
+  };
+  auto stash = [&](int b) {
+#pragma unroll
+    for (int u = 0; u < UA; ++u) *reinterpret_cast<u64*>(&As[b][(lrow + RP * u) * kWbRow + lq * 2]) = ra[u];
+#pragma unroll
+    for (int u = 0; u < UBn; ++u)
+      *reinterpret_cast<u64*>(&Bs[b][(lrow + RP * u) * kWbRow + lq * 2]) =
+          sh ? (rb0[u] >> sbits) | (rb1[u] << (64 - sbits)) : rb0[u];
+  };
+  if (total > 0) {
+    fetch();
+    stash(0);
+  }
+  __syncthreads();
+  for (int st = 0; st < total; ++st) {
+    const int b = st & 1;
+    if (st + 1 < total) fetch();
+    bf16x8 af[4], bfr[FJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      af[i] = *reinterpret_cast<const bf16x8*>(&As[b][(wm * 64 + i * 16 + r16) * kWbRow + g * 16]);
+#pragma unroll
+    for (int j = 0; j < FJ; ++j)
+      bfr[j] = *reinterpret_cast<const bf16x8*>(&Bs[b][(wn * 16 * FJ + j * 16 + r16) * kWbRow + g * 16]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    if (st + 1 < total) stash(b ^ 1);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < FJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int o = o0 + wm * 64 + i * 16 + g * 4 + e, c = c0 + wn * 16 * FJ + j * 16 + r16;
+        if (o < O && c < C) part[(((size_t)s * O + o) * C + c) * 9 + t] = acc[i][j][e];
+      }
+}
+
 }  // namespace
 
 // split forward / dgrad shape: 56 x 56 maps, cin 64 | 256, cout 64 | 256
@@ -652,6 +828,45 @@ static hipError_t k6_split_conv(const float* x, const float* w, const float* b, 
     h.in = hm; h.wt = ws; h.bias = b; h.outf = yn; h.R = N; h.cin = cin; h.cout = cout_p;
     h.split = 1; h.hsc = hsc; h.in_c = 0.f; h.in_s = 1.f; h.in_idx = 1; h.out_idx = -1; h.amax_idx = -1;
     h.w_exp = 0;
+    if ((e = launch_hmconv(h, st)) != hipSuccess) break;
+    hipLaunchKernelGGL(k6_nhwc_nchw_kernel, dim3((kHmSide * kHmSide + 63) / 64, (unsigned)((cout + 63) / 64), (unsigned)N),
+                       dim3(256), 0, st, yn, cout, cout_p, y);
+    e = hipGetLastError();
+  } while (false);
+  const hipError_t ef = hipFreeAsync(base, st);
+  return e != hipSuccess ? e : ef;
+}
+
+// k6_split_conv's call in precision "mixed": bf16 operands unscaled (no max /
+// bound passes), the non-split hmconv kernel in its linear mode
+static hipError_t k6_mixed_conv(const float* x, const float* w, const float* b, int N, int cin, int cout, int flip,
+                                float* y, hipStream_t st) {
+  const int cout_p = cout == 64 ? 128 : cout;
+  const size_t hm_bytes = (size_t)N * kHmRoiPos * cin * 2, ws_elems = (size_t)cout_p * 9 * cin;
+  const size_t nhwc = (size_t)N * kHmSide * kHmSide * cout_p;
+  char* buf = nullptr;
+  const size_t total = hm_bytes + ws_elems * 2 + nhwc * 4 + (size_t)cout_p * 4 + 256 * 4;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&buf), total, st);
+  if (e != hipSuccess) return e;
+  auto carve = [&](size_t bytes) { char* r = buf; buf += (bytes + 255) / 256 * 256; return r; };
+  char* base = buf;
+  __bf16* hm = reinterpret_cast<__bf16*>(carve(hm_bytes));
+  __bf16* ws = reinterpret_cast<__bf16*>(carve(ws_elems * 2));
+  float* yn = reinterpret_cast<float*>(carve(nhwc * 4));
+  float* zb = reinterpret_cast<float*>(carve((size_t)cout_p * 4));
+  do {
+    // (the border kernel counts 4 bytes a channel: cin / 2 of them)
+    hipLaunchKernelGGL(k6_hm_border_kernel, dim3((unsigned)N), dim3(256), 0, st, reinterpret_cast<_Float16*>(hm), cin / 2);
+    hipLaunchKernelGGL(k6_bias_sign_kernel, dim3((unsigned)((cout_p + 255) / 256)), dim3(256), 0, st, b, cout, cout_p, zb);
+    hipLaunchKernelGGL(k6_to_hm_bf_kernel, dim3((kHmSide * kHmSide + 63) / 64, (unsigned)(cin / 32), (unsigned)N),
+                       dim3(256), 0, st, x, cin, hm);
+    const long nw = (long)cout_p * 9 * cin;
+    hipLaunchKernelGGL(k6_pack_w_bf_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, w, flip ? cin : cout,
+                       flip ? cout : cin, flip, cout_p, ws);
+    if ((e = hipGetLastError()) != hipSuccess) break;
+    HmConvArgs h{};
+    h.in = hm; h.wt = ws; h.bias = zb; h.outf = yn; h.R = N; h.cin = cin; h.cout = cout_p;
+    h.split = 0; h.in_c = 0.f; h.in_s = 1.f; h.in_idx = -1; h.out_idx = -1; h.amax_idx = -1;
     if ((e = launch_hmconv(h, st)) != hipSuccess) break;
     hipLaunchKernelGGL(k6_nhwc_nchw_kernel, dim3((kHmSide * kHmSide + 63) / 64, (unsigned)((cout + 63) / 64), (unsigned)N),
                        dim3(256), 0, st, yn, cout, cout_p, y);
@@ -735,6 +950,69 @@ static hipError_t k6_wgrad(const float* x, const float* gy, int N, int C, int H,
   return e != hipSuccess ? e : ef;
 }
 
+// gw (and gb) in precision "mixed": k6_wgrad's GEMM, slices and sums on bf16
+// planes -- the plane pass rounds x and gy to bf16 once (half the bytes the
+// per-tap re-staging reads from L2), no max passes
+static hipError_t k6_wgrad_bf(const float* x, const float* gy, int N, int C, int H, int W, int O, float* gw, float* gb,
+                              hipStream_t st) {
+  const int W2 = W + 2, Qs = ((H + 2) * W2 + kWsK - 1) / kWsK * kWsK;
+  // guard elements at both ends of xP: a tap shifts a read by up to W + 3, and the
+  // kernel reads the aligned 8 elements around its 4 (3 below, 4 above); a multiple of 4
+  const int G = (W + 8 + 3) / 4 * 4;
+  const int TM = O > kWgT ? 256 : kWgT, TN = C > kWgT ? 256 : kWgT;
+  const int Cp = (C + TN - 1) / TN * TN, Op = (O + TM - 1) / TM * TM;
+  const int tiles = (Cp / TN) * (Op / TM) * 9;
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+      ncu = 256;
+  }
+  const long slots = (long)ncu * (TM * TN > kWgT * kWgT ? 1 : 2);   // as the split kernel's: the same slices
+  int ips = N;
+  long best = -1;
+  for (int i = 1; i <= N; ++i) {
+    const long S = (N + i - 1) / i, cost = ((S * tiles + slots - 1) / slots) * i;
+    if (best < 0 || cost < best) { best = cost; ips = i; }
+  }
+  const int S = (N + ips - 1) / ips;
+  const size_t xb = ((size_t)N * Cp * Qs + 2 * G) * 2, gyb = (size_t)N * Op * Qs * 2, pb = (size_t)S * O * C * 9 * 4;
+  const size_t sb = gb ? (size_t)N * O * 4 : 0;
+  char* buf = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&buf), xb + gyb + pb + sb + 1024, st);
+  if (e != hipSuccess) return e;
+  char* base = buf;
+  auto carve = [&](size_t bytes) { char* r = buf; buf += (bytes + 255) / 256 * 256; return r; };
+  __bf16* xP = reinterpret_cast<__bf16*>(carve(xb));
+  __bf16* gyP = reinterpret_cast<__bf16*>(carve(gyb));
+  float* part = reinterpret_cast<float*>(carve(pb));
+  float* psum = gb ? reinterpret_cast<float*>(carve(sb)) : nullptr;
+  do {
+    if ((e = hipMemsetAsync(xP, 0, (size_t)G * 2, st)) != hipSuccess) break;
+    if ((e = hipMemsetAsync(xP + G + (size_t)N * Cp * Qs, 0, (size_t)G * 2, st)) != hipSuccess) break;
+    hipLaunchKernelGGL(k6_plane_bf_kernel, dim3((unsigned)Cp, (unsigned)N), dim3(256), 0, st, x, C, H, W, Cp, Qs, xP + G,
+                       nullptr);
+    hipLaunchKernelGGL(k6_plane_bf_kernel, dim3((unsigned)Op, (unsigned)N), dim3(256), 0, st, gy, O, H, W, Op, Qs, gyP,
+                       psum);
+    if (gb) hipLaunchKernelGGL(k6_bias_finish_kernel, dim3((unsigned)((O + 255) / 256)), dim3(256), 0, st, psum, N, O, gb);
+    const dim3 grid((unsigned)(Cp / TN), (unsigned)(Op / TM), (unsigned)(9 * S));
+#define K6B_LAUNCH(M_, N_, F_)                                                                              \
+  hipLaunchKernelGGL((k6_wgrad_bf_kernel<M_, N_, F_>), grid, dim3(64 * M_ * N_), 0, st, gyP, xP + G, N, Op, Cp, O, \
+                     C, W2, Qs, ips, part)
+    if (TM == 256 && TN == 256) K6B_LAUNCH(4, 2, 8);
+    else if (TM == 256) K6B_LAUNCH(4, 2, 4);
+    else if (TN == 256) K6B_LAUNCH(2, 4, 4);
+    else K6B_LAUNCH(2, 2, 4);
+#undef K6B_LAUNCH
+    const long n = (long)O * C * 9;
+    hipLaunchKernelGGL(slice_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, S, n, gw);
+    e = hipGetLastError();
+  } while (false);
+  const hipError_t ef = hipFreeAsync(base, st);
+  return e != hipSuccess ? e : ef;
+}
+
 // gb [O] alone: plane sums of gy, summed over the images in order
 static hipError_t k6_bias(const float* gy, int N, int O, int H, int W, float* gb, hipStream_t st) {
   float* psum = nullptr;
@@ -749,11 +1027,15 @@ static hipError_t k6_bias(const float* gy, int N, int O, int H, int W, float* gb
 }
 
 hipError_t launch_conv3_forward(const float* x, const float* w, const float* b, int N, int C, int H, int W, int O,
-                                float* y, hipStream_t st) {
+                                float* y, int mixed, hipStream_t st) {
   if (N <= 0) return hipSuccess;
-  if (!k6_generic() && k6_split_ok(N, C, O, H, W)) return k6_split_conv(x, w, b, N, C, O, 0, y, st);
+  if (!k6_generic() && k6_split_ok(N, C, O, H, W))
+    return mixed ? k6_mixed_conv(x, w, b, N, C, O, 0, y, st) : k6_split_conv(x, w, b, N, C, O, 0, y, st);
   const dim3 grid((unsigned)((H * W + TB - 1) / TB), (unsigned)((O + TB - 1) / TB), (unsigned)N);
-  hipLaunchKernelGGL(conv3_gemm_kernel<C3_FWD>, grid, dim3(256), 0, st, x, w, nullptr, b, C, H, W, O, 0, 0, y);
+  if (mixed)
+    hipLaunchKernelGGL((conv3_gemm_kernel<C3_FWD, true>), grid, dim3(256), 0, st, x, w, nullptr, b, C, H, W, O, 0, 0, y);
+  else
+    hipLaunchKernelGGL(conv3_gemm_kernel<C3_FWD>, grid, dim3(256), 0, st, x, w, nullptr, b, C, H, W, O, 0, 0, y);
   return hipGetLastError();
 }
 
@@ -765,17 +1047,18 @@ size_t conv3_wgrad_slices(int N, int H, int W) {
 }
 
 hipError_t launch_conv3_backward(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
-                                 float* gx, float* gw, float* gb, float* wgrad_part, hipStream_t st) {
+                                 float* gx, float* gw, float* gb, float* wgrad_part, int mixed, hipStream_t st) {
   if (N <= 0) return hipSuccess;
   const int HW = H * W;
   const bool generic = k6_generic();
   if (gx && !generic && k6_split_ok(N, O, C, H, W)) {
-    const hipError_t e = k6_split_conv(gy, w, nullptr, N, O, C, 1, gx, st);
+    const hipError_t e = mixed ? k6_mixed_conv(gy, w, nullptr, N, O, C, 1, gx, st)
+                               : k6_split_conv(gy, w, nullptr, N, O, C, 1, gx, st);
     if (e != hipSuccess) return e;
     gx = nullptr;
   }
   if (gw && !generic) {
-    const hipError_t e = k6_wgrad(x, gy, N, C, H, W, O, gw, gb, st);
+    const hipError_t e = mixed ? k6_wgrad_bf(x, gy, N, C, H, W, O, gw, gb, st) : k6_wgrad(x, gy, N, C, H, W, O, gw, gb, st);
     if (e != hipSuccess) return e;
     gw = gb = nullptr;
   }
@@ -786,8 +1069,12 @@ hipError_t launch_conv3_backward(const float* x, const float* w, const float* gy
   }
   if (gx) {
     const dim3 grid((unsigned)((HW + TB - 1) / TB), (unsigned)((C + TB - 1) / TB), (unsigned)N);
-    hipLaunchKernelGGL(conv3_gemm_kernel<C3_DGRAD>, grid, dim3(256), 0, st, nullptr, w, gy, nullptr, C, H, W, O, 0, 0,
-                       gx);
+    if (mixed)
+      hipLaunchKernelGGL((conv3_gemm_kernel<C3_DGRAD, true>), grid, dim3(256), 0, st, nullptr, w, gy, nullptr, C, H, W, O,
+                         0, 0, gx);
+    else
+      hipLaunchKernelGGL(conv3_gemm_kernel<C3_DGRAD>, grid, dim3(256), 0, st, nullptr, w, gy, nullptr, C, H, W, O, 0, 0,
+                         gx);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -796,8 +1083,12 @@ hipError_t launch_conv3_backward(const float* x, const float* w, const float* gy
     const int S = (int)conv3_wgrad_slices(N, H, W);
     const int ks = 4096;   // a multiple of the K step (16); the last slice ends at N * H * W
     const dim3 grid((unsigned)((9 * C + TB - 1) / TB), (unsigned)((O + TB - 1) / TB), (unsigned)S);
-    hipLaunchKernelGGL(conv3_gemm_kernel<C3_WGRAD>, grid, dim3(256), 0, st, x, nullptr, gy, nullptr, C, H, W, O, ks,
-                       N * HW, wgrad_part);
+    if (mixed)
+      hipLaunchKernelGGL((conv3_gemm_kernel<C3_WGRAD, true>), grid, dim3(256), 0, st, x, nullptr, gy, nullptr, C, H, W, O,
+                         ks, N * HW, wgrad_part);
+    else
+      hipLaunchKernelGGL(conv3_gemm_kernel<C3_WGRAD>, grid, dim3(256), 0, st, x, nullptr, gy, nullptr, C, H, W, O, ks,
+                         N * HW, wgrad_part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const long n = (long)O * 9 * C;

@@ -1204,7 +1204,7 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
   constexpr int EMODE = MODE >= 0 ? MODE : (BN == 64 ? 1 : 0);
   static_assert(NTAP == 9 || (NTAP == 10 && EMODE == 2 && SPLIT && !DB), "tenth tap: KH downsample");
   static_assert(EMODE != 2 || (SPLIT && !DB), "KH epilogue: split, single fragment set");
-  static_assert(EMODE != 3 || SPLIT, "linear fp32 epilogue: split");
+  // (EMODE 3, the linear fp32 epilogue: split, or bf16 operands with us = 1 -- conv3x3's precision "mixed")
   constexpr int WAVES_N = BN / 64, WAVES_M = NW / WAVES_N;
   constexpr int WM = BMH / WAVES_M, FM = WM / 16, FN = 4;
   constexpr int AW = hm_awin<BMH>();
@@ -2279,10 +2279,41 @@ static hipError_t launch_hmconv_linear(const HmConvArgs& a0, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Linear mode on bf16 operands (split == 0: conv3x3's precision "mixed",
+// DESIGN.md §3i): the non-split K loop (one v_mfma_f32_16x16x32_bf16 per
+// fragment pair), fp32 NHWC output of acc + bias; the shapes and tiles of
+// launch_hmconv_linear, no scales
+static hipError_t launch_hmconv_linear_bf16(const HmConvArgs& a0, hipStream_t st) {
+  if (!a0.bias || (a0.cout != 256 && a0.cout != 128) || (a0.cin != 64 && a0.cin != 256) ||
+      (long)a0.R * HPP >= 0x7fffffffL)
+    return hipErrorInvalidValue;
+  HmConvArgs a = a0;
+  const long wt_bytes = (long)a.cout * 9 * a.cin * 2;
+  if (wt_bytes > kMaxDesc) return hipErrorInvalidValue;
+  a.wt_bytes = (int)wt_bytes;
+  a.m_off = 0;
+  a.r0 = 0;
+  a.stagger = 0;
+  a.out_idx = -1;
+  a.amax_idx = -1;
+  a.in_bytes = (int)std::min<long>((long)a.R * HPP * a.cin * 2, kMaxDesc);
+  const long rows = (long)a.R * HPP - HP;
+  if (a.cout == 256) {
+    const dim3 grid((unsigned)((rows + 223) / 224));
+    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, false, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, false, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
+  } else {
+    const dim3 grid((unsigned)((rows + BM - 1) / BM));
+    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, false, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, false, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_hmconv(const HmConvArgs& a0, hipStream_t st) {
   if (a0.R <= 0) return hipSuccess;
   if (a0.kh_ps) return launch_hmconv_kh(a0, st);
-  if (a0.outf && !a0.out && !a0.fin_w) return launch_hmconv_linear(a0, st);
+  if (a0.outf && !a0.out && !a0.fin_w) return a0.split ? launch_hmconv_linear(a0, st) : launch_hmconv_linear_bf16(a0, st);
   const bool fin = a0.fin_w != nullptr, split = a0.split != 0;
   if (a0.cin % (split ? 32 : 64) || (fin ? a0.cout != 64 : a0.cout % 128) ||
       (fin && (!a0.slot || !a0.heat || !a0.fin_b)) || (!fin && !a0.out) ||

@@ -516,8 +516,9 @@ hipError_t launch_conv1x1_nchw(const float* x, int N, int Cin, int HW, const flo
 hipError_t launch_fill(float* p, long n, float v, hipStream_t st);
 
 // ---- the heatmap head's 3x3 conv forward / backward on NCHW (conv3_grad.hip) ----
+// mixed != 0: bf16-rounded operands, one product per MAC; else the split path
 hipError_t launch_conv3_forward(const float* x, const float* w, const float* b, int N, int C, int H, int W, int O,
-                                float* y, hipStream_t st);
+                                float* y, int mixed, hipStream_t st);
 size_t conv3_wgrad_slices(int N, int H, int W);   // wgrad_part: slices * O * 9C floats
 hipError_t launch_conv3_backward(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
-                                 float* gx, float* gw, float* gb, float* wgrad_part, hipStream_t st);
+                                 float* gx, float* gw, float* gb, float* wgrad_part, int mixed, hipStream_t st);

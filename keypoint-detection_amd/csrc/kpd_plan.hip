@@ -1789,16 +1789,31 @@ int kpd_conv1x1(const float* x, int B, int Cin, int HW, const float* w, const fl
 
 int kpd_conv3x3_forward(const float* x, const float* w, const float* b, int N, int C, int H, int W, int O, float* y,
                         void* stream) {
+  return kpd_conv3x3_forward_prec(x, w, b, N, C, H, W, O, y, KPD_PRECISION_SPLIT, stream);
+}
+
+int kpd_conv3x3_forward_prec(const float* x, const float* w, const float* b, int N, int C, int H, int W, int O,
+                             float* y, int precision, void* stream) {
+  if (precision != KPD_PRECISION_SPLIT && precision != KPD_PRECISION_MIXED)
+    return fail(KPD_EINVAL, "conv3x3: precision must be KPD_PRECISION_SPLIT or KPD_PRECISION_MIXED");
   if (N < 0 || C <= 0 || H <= 0 || W <= 0 || O <= 0 || (N > 0 && (!x || !w || !y)))
     return fail(KPD_EINVAL, "bad conv3x3 arguments");
   if ((long)N * C * H * W >= (1L << 31) || (long)N * O * H * W >= (1L << 31) || (long)O * C * 9 >= (1L << 31))
     return fail(KPD_EINVAL, "conv3x3: tensors must stay below 2^31 elements");
-  HIP_TRY(launch_conv3_forward(x, w, b, N, C, H, W, O, y, reinterpret_cast<hipStream_t>(stream)));
+  HIP_TRY(launch_conv3_forward(x, w, b, N, C, H, W, O, y, precision == KPD_PRECISION_MIXED,
+                               reinterpret_cast<hipStream_t>(stream)));
   return KPD_OK;
 }
 
 int kpd_conv3x3_backward(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
                          float* gx, float* gw, float* gb, void* stream) {
+  return kpd_conv3x3_backward_prec(x, w, gy, N, C, H, W, O, gx, gw, gb, KPD_PRECISION_SPLIT, stream);
+}
+
+int kpd_conv3x3_backward_prec(const float* x, const float* w, const float* gy, int N, int C, int H, int W, int O,
+                              float* gx, float* gw, float* gb, int precision, void* stream) {
+  if (precision != KPD_PRECISION_SPLIT && precision != KPD_PRECISION_MIXED)
+    return fail(KPD_EINVAL, "conv3x3 backward: precision must be KPD_PRECISION_SPLIT or KPD_PRECISION_MIXED");
   if (N < 0 || C <= 0 || H <= 0 || W <= 0 || O <= 0 || (N > 0 && !gy) || (gx && !w) || (gw && !x))
     return fail(KPD_EINVAL, "bad conv3x3 backward arguments");
   if ((long)N * C * H * W >= (1L << 31) || (long)N * O * H * W >= (1L << 31) || (long)O * C * 9 >= (1L << 31))
@@ -1812,7 +1827,8 @@ int kpd_conv3x3_backward(const float* x, const float* w, const float* gy, int N,
   float* part = nullptr;
   if (gw && conv3_wgrad_slices(N, H, W)) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&part),
                                  sizeof(float) * conv3_wgrad_slices(N, H, W) * O * C * 9, st));
-  const hipError_t e = launch_conv3_backward(x, w, gy, N, C, H, W, O, gx, gw, gb, part, st);
+  const hipError_t e = launch_conv3_backward(x, w, gy, N, C, H, W, O, gx, gw, gb, part,
+                                             precision == KPD_PRECISION_MIXED, st);
   if (part) HIP_TRY(hipFreeAsync(part, st));
   HIP_TRY(e);
   return KPD_OK;

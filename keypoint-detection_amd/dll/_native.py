@@ -32,7 +32,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_plan_set_streams", "kpd_preprocess", "kpd_target_heatmaps", "kpd_keypoint_metrics",
            "kpd_heatmap_head", "kpd_keypoint_head", "kpd_backbone", "kpd_channel_attention", "kpd_decode_heatmaps",
            "kpd_roi_align", "kpd_conv1x1", "kpd_adaptive_heatmap_loss", "kpd_conv3x3_forward",
-           "kpd_conv3x3_backward", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
+           "kpd_conv3x3_backward", "kpd_conv3x3_forward_prec", "kpd_conv3x3_backward_prec", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
            "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features")
@@ -163,6 +163,10 @@ def load() -> ctypes.CDLL:
                                         c_void_p]
     lib.kpd_conv3x3_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p]
+    lib.kpd_conv3x3_forward_prec.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                             c_int, c_void_p]
+    lib.kpd_conv3x3_backward_prec.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p]
     lib.kpd_bn_train_forward.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                          c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kpd_bn_train_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
@@ -549,8 +553,21 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor])
     return out
 
 
-def conv3x3_forward(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """nn.Conv2d(k=3, padding=1) forward on NCHW device tensors (kpd_conv3x3_forward)."""
+# dll.ops.conv3x3's precisions (kpd_conv3x3_*_prec): the fp32-accurate split products, or bf16-rounded operands
+CONV3_PRECISIONS = {"split": KPD_PRECISION_SPLIT, "mixed": KPD_PRECISION_MIXED}
+
+
+def conv3_precision(precision: str) -> int:
+    try:
+        return CONV3_PRECISIONS[precision]
+    except (KeyError, TypeError):
+        raise ValueError(f"conv3x3 precision must be one of {sorted(CONV3_PRECISIONS)}, got {precision!r}") from None
+
+
+def conv3x3_forward(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                    precision: str = "split") -> torch.Tensor:
+    """nn.Conv2d(k=3, padding=1) forward on NCHW device tensors (kpd_conv3x3_forward_prec)."""
+    prec = conv3_precision(precision)
     x = _dev_f32(x, "x")
     N, C, H, W = x.shape
     w = weight.detach().to(x.device, torch.float32).contiguous()
@@ -560,15 +577,16 @@ def conv3x3_forward(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     y = torch.empty(N, w.shape[0], H, W, device=x.device)
     lib = load()
     with torch.cuda.device(x.device):
-        check(lib.kpd_conv3x3_forward(_ptr(x), _ptr(w), _ptr(b), N, C, H, W, w.shape[0], _ptr(y), _stream(x.device)),
-              "kpd_conv3x3_forward")
+        check(lib.kpd_conv3x3_forward_prec(_ptr(x), _ptr(w), _ptr(b), N, C, H, W, w.shape[0], _ptr(y), prec,
+                                           _stream(x.device)), "kpd_conv3x3_forward_prec")
     return y
 
 
 def conv3x3_backward(x: torch.Tensor, weight: torch.Tensor, grad_y: torch.Tensor, need_x: bool = True,
-                     need_w: bool = True, need_b: bool = True):
-    """Gradients of nn.Conv2d(k=3, padding=1) (kpd_conv3x3_backward): (gx, gw, gb),
+                     need_w: bool = True, need_b: bool = True, precision: str = "split"):
+    """Gradients of nn.Conv2d(k=3, padding=1) (kpd_conv3x3_backward_prec): (gx, gw, gb),
     None where not requested."""
+    prec = conv3_precision(precision)
     x = _dev_f32(x, "x")
     N, C, H, W = x.shape
     w = weight.detach().to(x.device, torch.float32).contiguous()
@@ -583,8 +601,8 @@ def conv3x3_backward(x: torch.Tensor, weight: torch.Tensor, grad_y: torch.Tensor
     gb = torch.empty(O, device=x.device) if need_b else None
     lib = load()
     with torch.cuda.device(x.device):
-        check(lib.kpd_conv3x3_backward(_ptr(x), _ptr(w), _ptr(gy), N, C, H, W, O, _ptr(gx), _ptr(gw), _ptr(gb),
-                                       _stream(x.device)), "kpd_conv3x3_backward")
+        check(lib.kpd_conv3x3_backward_prec(_ptr(x), _ptr(w), _ptr(gy), N, C, H, W, O, _ptr(gx), _ptr(gw), _ptr(gb),
+                                            prec, _stream(x.device)), "kpd_conv3x3_backward_prec")
     return gx, gw, gb
 
 

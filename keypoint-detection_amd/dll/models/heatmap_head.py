@@ -18,6 +18,10 @@ statistics updated; both native forward and backward), the final 1x1
 convolution and the sigmoid in torch ops.  ``loss.backward()`` and an
 optimiser step then work on the head, and ``eval()`` afterwards serves the
 updated weights and running statistics through the plan.
+``train_precision`` chooses the arithmetic of the train path's three 3x3
+convolutions: "split" (fp32-accurate, the default) or "mixed" (bf16-rounded
+operands, fp32 accumulation: DESIGN.md §3i; ``Trainer(use_amp=True)`` sets
+it).  It does not touch the eval path, the plan or ``precision``.
 """
 import ctypes
 import weakref
@@ -85,6 +89,7 @@ def _owner(m: nn.Module) -> "HeatmapHead":
 
 class HeatmapHead(nn.Module):
     precision = "split"   # "fp32" | "split" (fp32-accurate) | "mixed" (bf16 convs); the model sets its own
+    train_precision = "split"   # the train path's conv3x3 precision: "split" | "mixed" (bf16 operands, §3i)
 
     def __init__(self, config: HeatmapHeadConfig):
         super().__init__()
@@ -126,7 +131,7 @@ class HeatmapHead(nn.Module):
     def _conv_bn_relu(self, x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, p: float) -> torch.Tensor:
         """conv3x3 -> batch-statistics BN -> ReLU -> Dropout2d(p), as nn.BatchNorm2d
         and nn.Dropout2d behave in train mode; both operators native."""
-        x = conv3x3(x, conv.weight, conv.bias)
+        x = conv3x3(x, conv.weight, conv.bias, precision=self.train_precision)
         momentum = 0.0 if bn.momentum is None else bn.momentum
         if bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
@@ -144,9 +149,10 @@ class HeatmapHead(nn.Module):
         return x
 
     def _forward_train(self, x: torch.Tensor):
-        """The train path: fp32-accurate whatever ``precision`` says (the native
-        3x3 convolutions are the split-product ones of dll.ops.conv3x3, the
-        rest is fp32)."""
+        """The train path, whatever ``precision`` says: the native 3x3
+        convolutions of dll.ops.conv3x3 in ``train_precision`` (fp32-accurate
+        split products by default, bf16-rounded operands under "mixed"), the
+        rest in fp32."""
         _native._require_cuda(x, "x")
         x = x.float()
         att = None

@@ -5,7 +5,10 @@ forward and backward both run native (libkpd: kpd_conv3x3_forward /
 kpd_conv3x3_backward: fp32-accurate split f16 hi / lo MFMA products with fp32
 accumulation for the forward and dgrad at 56 x 56 with 64 | 256 channels and
 for every wgrad, exact fp32 products on the generic fallback; deterministic
-sums).  The
+sums).  With ``precision="mixed"`` the same three run on bf16-rounded
+operands, one v_mfma_f32_16x16x32_bf16 product per MAC with fp32 accumulation
+and no scale passes (kpd_conv3x3_*_prec): the arithmetic of
+``Trainer(use_amp=True)``; tensors, parameters and gradients stay fp32.  The
 reference gets these gradients from autograd in Trainer.train
 (dll/training/trainer.py:263,272).
 
@@ -33,29 +36,39 @@ from . import _native
 
 class Conv3x3Function(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]):
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], precision: str = "split"):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.bias_dtype = bias.dtype if bias is not None else None
-        return _native.conv3x3_forward(x, weight, bias).to(x.dtype)   # computed in fp32, returned like F.conv2d
+        ctx.precision = precision
+        # computed in fp32, returned like F.conv2d
+        return _native.conv3x3_forward(x, weight, bias, precision).to(x.dtype)
 
     @staticmethod
     def backward(ctx, grad_y: torch.Tensor):
         x, weight = ctx.saved_tensors
-        nx, nw, nb = ctx.needs_input_grad
-        gx, gw, gb = _native.conv3x3_backward(x, weight, grad_y, need_x=nx, need_w=nw, need_b=ctx.has_bias and nb)
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        gx, gw, gb = _native.conv3x3_backward(x, weight, grad_y, need_x=nx, need_w=nw, need_b=ctx.has_bias and nb,
+                                              precision=ctx.precision)
         if gw is not None:
             gw = gw.to(weight.dtype)
         if gx is not None:
             gx = gx.to(x.dtype)
         if gb is not None:
             gb = gb.to(ctx.bias_dtype)
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
-def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """F.conv2d(x, weight, bias, padding=1) with a native forward and backward."""
-    return Conv3x3Function.apply(x, weight, bias)
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+            precision: str = "split") -> torch.Tensor:
+    """F.conv2d(x, weight, bias, padding=1) with a native forward and backward.
+
+    precision "split" (default): fp32-accurate.  "mixed": every product of the
+    forward, the dgrad and the wgrad is of its two operands each rounded to
+    bf16 (nearest even) from its fp32 value, accumulated in fp32; the bias and
+    the bias gradient stay fp32.  Tensors are fp32 either way."""
+    _native.conv3_precision(precision)   # before any device check
+    return Conv3x3Function.apply(x, weight, bias, precision)
 
 
 class BnReluDropout2dFunction(torch.autograd.Function):

@@ -17,8 +17,19 @@ cache key includes the head's parameters, which change every step, so asking
 per step would re-pack every weight per step; ``roi_features`` never reads the
 (stale) head weights of that plan.
 
-Out of scope: training the trunk, the detector or KEYPOINT_HEAD, AMP
-(``use_amp=True`` raises), multi-GPU training.
+``use_amp=True`` is bf16 mixed precision: the head's three
+3x3 convolutions -- which are the step -- multiply bf16-rounded operands with
+fp32 accumulation in the forward, the dgrad and the wgrad
+(``head.train_precision = "mixed"``); parameters, gradients, optimizer state,
+batch norm, the attention blocks, the final 1x1 and the loss stay fp32 (fp32
+master weights).  bf16 has fp32's exponent range, so there is no loss scaling
+and ``scaler`` is None -- the reference's f16 autocast needs its GradScaler,
+this does not.  Checkpoints hold fp32 state only: a run may switch between
+the two modes at any ``resume``.  Validation runs the eval head as always.
+
+Out of scope: training the trunk, the detector or KEYPOINT_HEAD,
+``torch.autocast`` / ``GradScaler`` integration, f16 training, AMP on a CPU
+device (raises), multi-GPU training.
 """
 from __future__ import annotations
 
@@ -53,9 +64,10 @@ def batch_boxes(batch: Dict) -> torch.Tensor:
 class Trainer:
     def __init__(self, model: nn.Module, device: torch.device, train_dataloader, val_dataloader,
                  config: TrainingConfig, output_dir: Optional[Union[str, Path]] = None, use_amp: bool = False):
-        if use_amp:
-            raise NotImplementedError("AMP training is out of scope: the native train path of the heatmap head is "
-                                      "fp32-accurate (DESIGN.md §3h); construct the Trainer with use_amp=False")
+        if use_amp and torch.device(device).type != "cuda":
+            raise NotImplementedError("AMP training runs on the native bf16 kernels of the heatmap head's train path "
+                                      "(DESIGN.md §3i), which need a GPU device; construct the Trainer with "
+                                      "use_amp=False")
         if not hasattr(model, "heatmap_head"):
             raise TypeError("Trainer trains model.heatmap_head; pass a MultiPersonKeypointModel")
         self.device = torch.device(device)
@@ -67,7 +79,10 @@ class Trainer:
         self.output_dir = Path(output_dir) if output_dir else None
         if self.output_dir:
             self.output_dir.mkdir(parents=True, exist_ok=True)
-        self.use_amp = False
+        # bf16 operands in the head's 3x3 convolutions, fp32 everything else; no loss scaling (module docstring)
+        self.use_amp = bool(use_amp)
+        self.scaler = None
+        self.head.train_precision = "mixed" if self.use_amp else "split"
         self.model.eval()
         self.optimizer = self._create_optimizer()
         sc = config.lr_scheduler

@@ -6,13 +6,16 @@ kpd_roi_features + kpd_roi_targets -> HeatmapHead train step -> checkpoints.
 
     python scripts/train.py --config configs/default_config.yaml --data_dir data/ \
         --output_dir runs/head [--model best_model.pth|synthetic] [--resume runs/head/checkpoint_epoch_5.pth] \
-        [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed]
+        [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed] [--amp]
 
 ``--model`` gives the starting weights (a checkpoint, or ``synthetic`` for the
 seeded synthetic state dict; default: the freshly initialised model);
 ``--resume`` continues a run from one of its checkpoints (model, optimizer,
 epoch, history).  ``--max-steps`` bounds the batches of every train and
-validation epoch.  One JSON line per epoch goes to stdout: epoch, train_loss,
+validation epoch.  ``--amp`` trains in bf16 mixed precision
+(``Trainer(use_amp=True)``: bf16 operands in the head's 3x3 convolutions, fp32
+master weights, no loss scaling); ``--precision`` is the plan's, for the trunk
+features and validation.  One JSON line per epoch goes to stdout: epoch, train_loss,
 loss (validation), avg_ADE, pck_*, learning_rate, steps, skipped_steps, seconds.
 Every argument is checked before the device is touched.
 """
@@ -53,6 +56,7 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--augment", action="store_true", help="augment the train split (also: augmentation.enabled)")
     ap.add_argument("--precision", default="split", choices=["split", "fp32", "mixed"])
+    ap.add_argument("--amp", action="store_true", help="bf16 mixed-precision training (Trainer use_amp=True)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     for name in ("epochs", "batch_size", "max_steps"):
@@ -104,7 +108,7 @@ def main(argv=None):
         model = _fresh_model(cfg, device, args.precision)
     else:
         model = load_model(args.model, cfg, device, args.precision)
-    trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir)
+    trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp)
     trainer.max_steps = args.max_steps
     if args.resume is not None:
         trainer.resume(args.resume)

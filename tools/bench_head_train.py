@@ -23,9 +23,15 @@ resident tensors; after warm-ups the variants alternate `--rounds` times and
 the medians are reported.  The chain's results are checked against the fused
 operator's once.  One JSON line; the tool sets no pass/fail threshold.
 
+`--amp` measures instead one comparison: the head step with
+`train_precision` "split" against "mixed" (bf16 operands in the three 3x3
+convolutions) -- two heads with the same weights on the same
+inputs, alternated: medians with min-max, the ratio, and the max abs
+difference of the first step's loss between the two.
+
 The measurement runs in a child process under its own `timeout`:
 
-    python tools/bench_head_train.py [--rois 64] [--rounds 7] [--inner 4] [--timeout 600]
+    python tools/bench_head_train.py [--rois 64] [--rounds 7] [--inner 4] [--timeout 600] [--amp]
 """
 import argparse
 import copy
@@ -70,6 +76,42 @@ def worker(a):
             for k, fn in variants.items():
                 ms[k].append(timed(fn, inner))
         return {k: statistics.median(v) for k, v in ms.items()}, ms
+
+    if a.amp:
+        heads = {}
+        for prec in ("split", "mixed"):
+            h = HeatmapHead(HeatmapHeadConfig())
+            h.load_state_dict(synthetic_state_dict(h.state_dict(), seed=7))
+            h.train_precision = prec
+            heads[prec] = h.to(dev).train()
+        R = a.rois
+        xh = torch.rand(R, 64, 56, 56, generator=g).to(dev)
+        gt = generate_target_heatmap((torch.rand(R, 17, 2, generator=g) * 0.8 + 0.1).to(dev), (56, 56), sigma=3.0)
+        crit = AdaptiveHeatmapLoss()
+        first = {}
+
+        def step(prec):
+            heads[prec].zero_grad(set_to_none=True)
+            loss = crit(heads[prec](xh)[0], gt)
+            loss.backward()
+            return loss.detach()
+
+        for prec in heads:   # the same dropout masks in both first steps
+            torch.manual_seed(a.seed)
+            first[prec] = float(step(prec))
+        med, ms = alternate({p: (lambda p=p: step(p)) for p in heads}, max(1, a.inner // 2))
+        spread = max(max(ms[p]) - min(ms[p]) for p in heads)
+        print(json.dumps({
+            "metric": "head_train_amp_ms", "rois": R, "rounds": a.rounds, "inner": max(1, a.inner // 2),
+            "split_ms": round(med["split"], 3), "mixed_ms": round(med["mixed"], 3),
+            "split_ms_min_max": [round(min(ms["split"]), 3), round(max(ms["split"]), 3)],
+            "mixed_ms_min_max": [round(min(ms["mixed"]), 3), round(max(ms["mixed"]), 3)],
+            "split_ms_all": [round(v, 3) for v in ms["split"]], "mixed_ms_all": [round(v, 3) for v in ms["mixed"]],
+            "mixed_over_split": round(med["mixed"] / med["split"], 3),
+            "gain_ms": round(med["split"] - med["mixed"], 3), "larger_spread_ms": round(spread, 3),
+            "first_loss": {k: v for k, v in first.items()},
+            "first_loss_max_abs_diff": abs(first["split"] - first["mixed"])}))
+        return 0
 
     res = {"metric": "head_train_ms", "rois": a.rois, "rounds": a.rounds, "inner": a.inner, "operator": []}
 
@@ -178,6 +220,7 @@ def main():
     ap.add_argument("--inner", type=int, default=4, help="back-to-back calls per timed interval")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--timeout", type=int, default=600, help="seconds the measuring child may take")
+    ap.add_argument("--amp", action="store_true", help="head step, train_precision split against mixed")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.worker:

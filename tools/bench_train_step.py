@@ -21,9 +21,15 @@ Every variant is timed with HIP events around `--inner` back-to-back calls on
 resident tensors; after warm-ups the variants alternate `--rounds` times and
 the medians are reported.  One JSON line; the tool sets no pass/fail threshold.
 
+`--amp` measures instead one comparison: `Trainer.train_step` of a trainer
+built with `use_amp=False` against one built with `use_amp=True` (bf16
+operands in the head's 3x3 convolutions) -- two models from the
+same weights on the same batch, alternated: medians with min-max, the ratio,
+and the max abs difference of the first step's loss between the two.
+
 The measurement runs in a child process under its own `timeout`:
 
-    python tools/bench_train_step.py [--images 64] [--rounds 7] [--inner 3] [--timeout 600]
+    python tools/bench_train_step.py [--images 64] [--rounds 7] [--inner 3] [--timeout 600] [--amp]
 """
 import argparse
 import json
@@ -76,7 +82,7 @@ def worker(a):
     cfg = TrainingConfig()
     model = MultiPersonKeypointModel(ModelConfig(), cfg)
     model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=0))
-    trainer = Trainer(model, dev, [], [], cfg)
+    trainer = None if a.amp else Trainer(model, dev, [], [], cfg)
     image = synthetic_images(B, 3, 256, 192, seed=a.seed + 1, device=dev)
     boxes = synthetic_boxes(B, P, seed=a.seed + 2, device=dev)
     g = torch.Generator().manual_seed(a.seed + 3)
@@ -84,6 +90,28 @@ def worker(a):
     kp = boxes[:, :, None, :2] - boxes[:, :, None, 2:] / 2 + uv * boxes[:, :, None, 2:]
     vis = torch.randint(0, 3, (B, P, K), generator=g).float().to(dev)
     batch = {"image": image, "bboxes": [boxes], "keypoints": kp, "visibilities": vis}
+    if a.amp:
+        trainers = {}
+        for name, amp in (("split", False), ("amp", True)):
+            m = MultiPersonKeypointModel(ModelConfig(), cfg)
+            m.load_state_dict(synthetic_state_dict(m.state_dict(), seed=0))
+            trainers[name] = Trainer(m, dev, [], [], cfg, use_amp=amp)
+        first = {}
+        for k, t in trainers.items():   # the same dropout masks in both first steps
+            torch.manual_seed(a.seed)
+            first[k] = float(t.train_step(batch)["loss"])
+        inner = max(1, a.inner // 2)
+        med, ms = alternate({k: (lambda t=t: t.train_step(batch)) for k, t in trainers.items()}, inner)
+        out = {"metric": "train_step_amp_ms", "images": B, "persons": P, "rois": B * P, "rounds": a.rounds,
+               "inner": inner}
+        out.update(report(med, ms, ("split", "amp")))
+        spread = max(max(ms[k]) - min(ms[k]) for k in trainers)
+        out.update({k + "_ms_all": [round(v, 4) for v in ms[k]] for k in trainers})   # every timed interval
+        out.update(amp_over_split=round(med["amp"] / med["split"], 3), gain_ms=round(med["split"] - med["amp"], 4),
+                   larger_spread_ms=round(spread, 4), first_loss=first,
+                   first_loss_max_abs_diff=abs(first["split"] - first["amp"]))
+        print(json.dumps(out))
+        return 0
     rows = torch.arange(B * P, dtype=torch.int32, device=dev)
     plan = model.native_plan(dev)
     res = {"metric": "train_step_ms", "images": B, "persons": P, "rounds": a.rounds, "inner": a.inner}
@@ -175,6 +203,7 @@ def main():
     ap.add_argument("--inner", type=int, default=3, help="back-to-back calls per timed interval")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--timeout", type=int, default=600, help="seconds the measuring child may take")
+    ap.add_argument("--amp", action="store_true", help="train_step, use_amp=False against use_amp=True")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.worker:
