@@ -108,7 +108,9 @@ int kpd_plan_set_detector(kpd_plan* plan, float conf_threshold, float nms_iou_th
 
 /* Copy an internal buffer recorded by the last kpd_forward into `dst`
  * (device memory, `bytes` long).  Names: "feat0" ([B][Hf][Wf][128] NHWC f32),
- * "scores" ([B][128] f32), "roi" ([R][56][56][64] f32), "tap0".."tap3".
+ * "scores" ([B][128] f32), "roi" ([R][56][56][64] f32), "tap0".."tap3";
+ * with KPD_FLAG_DETECT the NMS's inputs "pd_boxes" ([B][28224][4] cxcywh f32)
+ * and "pd_scores" ([B][28224] f32, -inf where score <= conf_threshold).
  * Writes the buffer size to *size_out when dst == NULL. */
 int kpd_debug_copy(kpd_plan* plan, const char* name, void* dst, size_t bytes, size_t* size_out,
                    void* stream);

@@ -1105,6 +1105,10 @@ static int stage_detect(Pass& ps, const FwdArgs& a) {
     HIP_TRY(launch_person_decode(w.pd_head, B, p->pd.cout_p, p->anchors, a.H, a.W, p->det_conf, w.pd_boxes,
                                  w.pd_scores, ps.st));
   }
+  if (ps.debug) {   // the NMS's inputs: every candidate box, scores -inf where score <= conf
+    p->debug["pd_boxes"] = {w.pd_boxes, sizeof(float) * (size_t)B * 56 * 56 * 9 * 4};
+    p->debug["pd_scores"] = {w.pd_scores, sizeof(float) * (size_t)B * 56 * 56 * 9};
+  }
   HIP_TRY(launch_nms_sets(w.pd_boxes, w.pd_scores, B, 56 * 56 * 9, p->det_iou, a.P, a.P, w.pd_keep, w.pd_nkeep,
                           w.pd_alive, ps.st, 1, a.boxes, a.box_scores));
   return KPD_OK;

@@ -167,8 +167,14 @@ __global__ __launch_bounds__(1024) void nms_reg_kernel(const float* __restrict__
     __shared__ int sh_cnt;
     __shared__ int l_idx[kNmsList];
     __shared__ float l_sc[kNmsList];
-    auto key_of = [](float x) {   // order-preserving map of a float to unsigned (every alive key >= 0x007fffff)
+    // order-preserving map of a float to unsigned (every alive key >= 0x007fffff).
+    // -0.0 takes +0.0's key: better() ranks the two zeros as equal scores (lower
+    // index first), as the full pass and n <= 1024 do.  With a key of its own
+    // (0x7fffffff) every -0.0 would rank below every +0.0, and S could hold the
+    // +0.0 candidates without the -0.0 ones of lower index.
+    auto key_of = [](float x) {
       const unsigned b = __float_as_uint(x);
+      if (b == 0x80000000u) return b;
       return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     };
     if (tid == 0) { sh_total = 0u; sh_cnt = 0; sh_prefix = 0u; sh_need = kNmsPrefix; }
