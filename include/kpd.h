@@ -770,6 +770,71 @@ int kpd_bn_train_backward(const float* x, const float* gy, int N, int C, int H, 
                           const float* beta, const float* drop, const float* save_mean, const float* save_invstd,
                           int flags, float* gx, float* ggamma, float* gbeta, void* stream);
 
+/* Training side: the person detector on frozen trunk features.
+ * The reference has no detection loss, no anchor matching and no box encoding:
+ * the rules are build-defined, like the eval detector's glue, and pinned to
+ * the float64 restatement tests/det_train_ref.py.  A = 28,224 anchors in the
+ * candidate order (i, j, a) of the eval detector; anchor n is (ax, ay, aw, ah)
+ * = (anchors[n][0], anchors[n][1], anchors[n][2] / img_w, anchors[n][3] /
+ * img_h) in fp32.  GT boxes [B][G][4] are normalised (cx, cy, w, h), 0 <= G <=
+ * KPD_DET_MAX_GT; a row is absent if all four values are 0, if w <= 0 or
+ * h <= 0, or if any value is NaN.  Every entry checks its arguments before any
+ * device work (KPD_EINVAL, the argument named), takes scratch from the
+ * stream-ordered allocator and never synchronises the host.
+ *
+ * The detector's input: the forward's own stages -- body, laterals, FPN level
+ * 0 at every pixel -- then the adaptive average pool to the 56 x 56 anchor
+ * grid, summed in the order of the eval detector's pool.  image [B][C][H][W]
+ * -> out [B][3136][128] (cell i * 56 + j, channel).  Needs the backbone and
+ * fpn weights only; shares the plan's workspace as the ROI-feature entry does
+ * (debug buffers are dropped), on the caller's stream, never captured. */
+#define KPD_DET_ANCHORS 28224
+#define KPD_DET_MAX_GT 64
+int kpd_detector_features(kpd_plan* plan, const float* image, int B, int C, int H, int W, float* out, void* stream);
+
+/* Anchor matching.  IoU in fp32 with the operation order of the NMS's IoU
+ * (eps 1e-16), no contraction.  Per image and anchor n: best = the maximum IoU
+ * over the present GTs, arg = its slot (ties: the lower slot); best >= pos_thr:
+ * assign[n] = arg; neg_thr <= best < pos_thr: -2 (ignored); otherwise -1
+ * (negative).  Then, for each present GT g with gmax_g = max_n IoU(n, g) > 0,
+ * every anchor with IoU(n, g) >= gmax_g - tie_eps gets assign[n] = its own arg
+ * (low-quality matches; overrides -1 / -2).  n_pos[b] = the number of
+ * assign >= 0; an image without a present GT is all -1.  assign [B][A] int32,
+ * n_pos [B] int32, gt_best [B][G] (gmax; 0 for an absent row; nullable).
+ * gt_boxes may be NULL when G = 0.  Two launches: the per-GT maxima by
+ * atomicMax on the bit pattern of the non-negative IoU (order-independent),
+ * then the assignment.  pos_thr in (0, 1], neg_thr in [0, pos_thr], tie_eps
+ * >= 0. */
+int kpd_detector_targets(const float* anchors, const float* gt_boxes, int B, int G, int img_h, int img_w,
+                         float pos_thr, float neg_thr, float tie_eps, int32_t* assign, int32_t* n_pos,
+                         float* gt_best, void* stream);
+
+/* Detection loss and the gradients of box_heads[0] / cls_heads[0].  pooled
+ * [B][3136][128] (the features entry above), box_w [36][128], box_b [36],
+ * cls_w [9][128], cls_b [9], assign / n_pos from the matching.  Per cell, d =
+ * the 36 box deltas and z = the 9 logits of the 1x1 heads (exact fp32
+ * products, fp32 accumulation).  Class term, with t = [assign >= 0], p =
+ * sigmoid(z): FL = -alpha (1-p)^gamma log p (t = 1), -(1-alpha) p^gamma
+ * log(1-p) (t = 0), the logs through a stable softplus; ignored anchors
+ * contribute 0.  Box term on positives: smooth-L1 (beta) of d - target, target
+ * = ((gcx-ax)/aw, (gcy-ay)/ah, log(gw/aw), log(gh/ah)), the decode's inverse
+ * without its exp clip.  N = max(1, sum_b n_pos[b]), read on the device.
+ *   loss[0] = (sum FL + box_weight * sum SL1) / N, loss[1] = sum FL / N,
+ *   loss[2] = sum SL1 / N
+ * and g_* = d loss[0] / d parameter in closed form, each of the parameter's
+ * shape; the four gradient outputs are given together, or all NULL for the
+ * loss alone (the same loss bits).  One fused pass over pooled (no head map or
+ * gradient map goes through memory) with per-workgroup partials, fp32 within a
+ * block of 56 cells and across the blocks a workgroup owns (a map that depends
+ * on B alone), and one launch that sums the partials in index order in
+ * double: no floating-point atomics, two calls are bit-identical.  alpha in
+ * [0, 1], gamma >= 0, beta > 0, box_weight >= 0. */
+int kpd_detector_loss(const float* pooled, const float* box_w, const float* box_b, const float* cls_w,
+                      const float* cls_b, const float* anchors, const float* gt_boxes, const int32_t* assign,
+                      const int32_t* n_pos, int B, int G, int img_h, int img_w, float alpha, float gamma, float beta,
+                      float box_weight, float* loss, float* g_box_w, float* g_box_b, float* g_cls_w, float* g_cls_b,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

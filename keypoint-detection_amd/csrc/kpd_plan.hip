@@ -1649,6 +1649,37 @@ int kpd_roi_features(kpd_plan* p, const float* image, int B, int C, int H, int W
   return KPD_OK;
 }
 
+// The detector's training input: forward_one's stages up to
+// FPN level 0 at every pixel (a pass without boxes stores all of it), then the
+// 56 x 56 adaptive pool of the eval detector's unfused path, whose sums round
+// as the fused person_detect_kernel's.  Eager, on the caller's stream, in
+// workspace 0, the host-side workspace state moving as kpd_roi_features' does.
+int kpd_detector_features(kpd_plan* p, const float* image, int B, int C, int H, int W, float* out, void* stream) {
+  if (!p) return fail(KPD_EINVAL, "null plan");
+  if (!image || B <= 0 || H < 32 || W < 32) return fail(KPD_EINVAL, "bad image shape");
+  if (C != p->in_ch) return fail(KPD_EINVAL, "image channels do not match backbone in_channels");
+  if (!out) return fail(KPD_EINVAL, "null output pointer");
+  if (!p->finalized) return fail(KPD_ESTATE, "plan not finalized");
+  if (!p->has_body || !p->has_fpn) return fail(KPD_ESTATE, "plan lacks backbone.body / backbone.fpn weights");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIP_TRY(hipSetDevice(p->device));
+  p->debug.clear();   // they point into the workspace this call rewrites
+  if (p->path_on) p->path.e.clear();
+  const int cap = max_pass_images(H, W), npass = (B + cap - 1) / cap;
+  for (int q = 0; q < npass; ++q) {
+    const int b0 = (int)((long)B * q / npass), b1 = (int)((long)B * (q + 1) / npass), nb = b1 - b0;
+    const PathScope path_scope(p);
+    Pass ps;
+    const float* taps[4] = {};
+    if (int rc = begin_pass(ps, p, 0, false, nb, H, W, 0, 0, 0, st)) return rc;
+    if (int rc = stage_body(ps, image + (size_t)b0 * C * H * W, C, taps)) return rc;
+    if (int rc = stage_laterals(ps, taps, false)) return rc;
+    if (int rc = stage_level0(ps, nullptr)) return rc;
+    HIP_TRY(launch_adaptive_pool56(ps.w->feat, nb, ps.d.Hf, ps.d.Wf, 128, out + (size_t)b0 * 3136 * 128, st));
+  }
+  return KPD_OK;
+}
+
 int kpd_backbone_body(kpd_plan* p, const float* image, int B, int C, int H, int W, float* feat0, float* feat1,
                       float* feat2, float* feat3, void* stream) {
   if (!p || !p->finalized) return fail(KPD_ESTATE, "plan not finalized");

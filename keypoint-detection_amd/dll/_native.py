@@ -35,7 +35,8 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_conv3x3_backward", "kpd_conv3x3_forward_prec", "kpd_conv3x3_backward_prec", "kpd_plan_set_graphs", "kpd_backbone_body", "kpd_backbone_fpn",
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
-           "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features")
+           "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features", "kpd_detector_features",
+           "kpd_detector_targets", "kpd_detector_loss")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -69,6 +70,8 @@ FLAG_FULL_LEVEL0 = 4   # store all of FPN level 0 (debug copy "feat0"); default:
 FPN_IN_CHANNELS = (16, 24, 48, 576)   # LightweightFPN's lateral input widths (backbone.py)
 HEAD_CHANNEL_ATT, HEAD_SPATIAL_ATT, HEAD_CONVS, HEAD_ALL = 1, 2, 4, 7
 BN_RELU = 1            # KPD_BN_RELU
+DET_ANCHORS = 28224    # KPD_DET_ANCHORS: 56 x 56 cells x 9 anchors, candidate order (i, j, a)
+DET_MAX_GT = 64        # KPD_DET_MAX_GT: ground-truth slots per image
 DECODE_ARGMAX, DECODE_SUBPIXEL, DECODE_SOFTARGMAX, DECODE_MODEL = 0, 1, 2, 3
 STAGES = ("body", "fpn_lateral", "fpn0", "topk", "person_detect", "roi_align", "hm_attention", "hm_conv1",
           "hm_conv2", "hm_conv3", "hm_final_decode", "keypoint_head")
@@ -175,6 +178,10 @@ def load() -> ctypes.CDLL:
                                     c_void_p, c_void_p, c_void_p]
     lib.kpd_roi_features.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                      c_void_p, c_void_p]
+    lib.kpd_detector_features.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.kpd_detector_targets.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.kpd_detector_loss.argtypes = [c_void_p] * 9 + [c_int] * 4 + [c_float] * 4 + [c_void_p] * 6
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
@@ -387,6 +394,23 @@ class Plan:
                                             _stream(self.device)), "kpd_roi_features")
         return out
 
+    def detector_features(self, image: torch.Tensor) -> torch.Tensor:
+        """The person detector's input (kpd_detector_features): image [B,C,H,W]
+        -> [B,3136,128], FPN level 0 adaptive-average-pooled to the 56 x 56
+        anchor grid (cell i * 56 + j, channel), as the eval detector pools it.
+        No head runs and no host synchronisation happens."""
+        image = _dev_f32(image, "image")
+        if image.dim() != 4:
+            raise ValueError(f"image must be [B, C, H, W], got {tuple(image.shape)}")
+        B, C, H, W = image.shape
+        out = torch.empty(B, 3136, 128, device=image.device)
+        if B == 0:
+            return out
+        with torch.cuda.device(self.device):
+            check(self.lib.kpd_detector_features(self.h, _ptr(image), B, C, H, W, _ptr(out), _stream(self.device)),
+                  "kpd_detector_features")
+        return out
+
     def debug_buffer(self, name: str) -> torch.Tensor:
         n = ctypes.c_size_t()
         check(self.lib.kpd_debug_copy(self.h, name.encode(), None, 0, ctypes.byref(n), None), "kpd_debug_copy")
@@ -461,6 +485,80 @@ def roi_targets(keypoints: torch.Tensor, visibilities: torch.Tensor, boxes: torc
                                      int(W), float(sigma), _ptr(heat), _ptr(weight), _stream(keypoints.device)),
               "kpd_roi_targets")
     return heat, weight
+
+
+def _det_inputs(anchors: torch.Tensor, gt_boxes: Optional[torch.Tensor], B: int, image_size):
+    """(anchors [28224,4], gt [B,G,4] or None, G, H, W) for the detector-training entries."""
+    anchors = _dev_f32(anchors, "anchors")
+    if tuple(anchors.shape) != (DET_ANCHORS, 4):
+        raise ValueError(f"anchors must be [{DET_ANCHORS}, 4], got {tuple(anchors.shape)}")
+    H, W = (int(v) for v in image_size)
+    if gt_boxes is None:
+        return anchors, None, 0, H, W
+    gt = _dev_f32(gt_boxes, "gt_boxes").to(anchors.device)
+    if gt.dim() != 3 or gt.size(0) != B or gt.size(2) != 4:
+        raise ValueError(f"gt_boxes must be [{B}, G, 4], got {tuple(gt.shape)}")
+    G = gt.size(1)
+    if G > DET_MAX_GT:
+        raise ValueError(f"gt_boxes holds {G} slots per image; the matching takes at most {DET_MAX_GT}")
+    return anchors, (gt if G > 0 else None), G, H, W
+
+
+def detector_targets(anchors: torch.Tensor, gt_boxes: Optional[torch.Tensor], batch: int, image_size,
+                     pos_thr: float = 0.5, neg_thr: float = 0.4, tie_eps: float = 1e-5, want_best: bool = False):
+    """kpd_detector_targets: anchors [28224,4] (the PERSON_HEAD buffer), gt_boxes
+    [B,G,4] cxcywh normalised (None or G = 0: no labels), image_size (H, W) ->
+    (assign [B,28224] int32: GT slot, -1 negative, -2 ignored; n_pos [B] int32;
+    gt_best [B,G] or None).  No host synchronisation."""
+    anchors, gt, G, H, W = _det_inputs(anchors, gt_boxes, int(batch), image_size)
+    B = int(batch)
+    dev = anchors.device
+    assign = torch.empty(B, DET_ANCHORS, dtype=torch.int32, device=dev)
+    n_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    best = torch.empty(B, G, device=dev) if want_best else None
+    with torch.cuda.device(dev):
+        check(load().kpd_detector_targets(_ptr(anchors), _ptr(gt), B, G, H, W, float(pos_thr), float(neg_thr),
+                                          float(tie_eps), _ptr(assign), _ptr(n_pos),
+                                          _ptr(best) if G > 0 else None, _stream(dev)), "kpd_detector_targets")
+    return assign, n_pos, best
+
+
+def detector_loss(pooled: torch.Tensor, box_weight: torch.Tensor, box_bias: torch.Tensor, cls_weight: torch.Tensor,
+                  cls_bias: torch.Tensor, anchors: torch.Tensor, gt_boxes: Optional[torch.Tensor],
+                  assign: torch.Tensor, n_pos: torch.Tensor, image_size, alpha: float = 0.25, gamma: float = 2.0,
+                  beta: float = 1.0 / 9, box_weight_factor: float = 1.0, want_grad: bool = True):
+    """kpd_detector_loss: pooled [B,3136,128], the four parameters of
+    box_heads[0] / cls_heads[0] (nn.Conv2d shapes or flat), assign / n_pos from
+    detector_targets -> (loss [3] = total, class part, box part; (g_box_w
+    [36,128], g_box_b [36], g_cls_w [9,128], g_cls_b [9]) or None without
+    want_grad).  No host synchronisation."""
+    pooled = _dev_f32(pooled, "pooled")
+    if pooled.dim() != 3 or tuple(pooled.shape[1:]) != (3136, 128):
+        raise ValueError(f"pooled must be [B, 3136, 128], got {tuple(pooled.shape)}")
+    B, dev = pooled.size(0), pooled.device
+    anchors, gt, G, H, W = _det_inputs(anchors.to(dev), gt_boxes, B, image_size)
+    prm = []
+    for t, n, name in ((box_weight, 36 * 128, "box_weight"), (box_bias, 36, "box_bias"),
+                       (cls_weight, 9 * 128, "cls_weight"), (cls_bias, 9, "cls_bias")):
+        t = _dev_f32(t.detach(), name).to(dev)
+        if t.numel() != n:
+            raise ValueError(f"{name} must hold {n} values, got {tuple(t.shape)}")
+        prm.append(t)
+    for t, shape, name in ((assign, (B, DET_ANCHORS), "assign"), (n_pos, (B,), "n_pos")):
+        _require_cuda(t, name)
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous int32 tensor {list(shape)} on {dev}")
+    loss = torch.empty(3, device=dev)
+    grads = None
+    if want_grad:
+        grads = (torch.empty(36, 128, device=dev), torch.empty(36, device=dev), torch.empty(9, 128, device=dev),
+                 torch.empty(9, device=dev))
+    gp = [_ptr(g) for g in grads] if want_grad else [None] * 4
+    with torch.cuda.device(dev):
+        check(load().kpd_detector_loss(_ptr(pooled), *[_ptr(t) for t in prm], _ptr(anchors), _ptr(gt), _ptr(assign),
+                                       _ptr(n_pos), B, G, H, W, float(alpha), float(gamma), float(beta),
+                                       float(box_weight_factor), _ptr(loss), *gp, _stream(dev)), "kpd_detector_loss")
+    return loss, grads
 
 
 def decode_heatmaps(heat: torch.Tensor, mode: int, param: float = 0.0):

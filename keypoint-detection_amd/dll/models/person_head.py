@@ -4,8 +4,12 @@ Parameters and the ``anchors`` buffer keep the reference names
 (``box_heads.{0-3}``, ``cls_heads.{0-3}``, ``anchors`` [56*56*9, 4]).
 ``box_iou`` and ``non_max_suppression`` keep the reference signatures;
 ``non_max_suppression`` runs the native greedy NMS (csrc/nms.hip) for device
-tensors.
+tensors.  ``detection_loss`` and ``init_detection_bias`` are the training side
+of box_heads[0] / cls_heads[0], the only heads the eval detector reads
+(the reference has none).
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -60,6 +64,23 @@ class PERSON_HEAD(nn.Module):
         """Greedy NMS (reference :96-139) on the device; returns a CPU int64 index
         tensor like the reference."""
         return _native.nms(boxes, scores, iou_threshold, max_output_size or 0).cpu()
+
+    def init_detection_bias(self, prior: float = 0.01) -> None:
+        """Start every anchor at score ``prior``: cls_heads[0].bias =
+        -log((1 - prior) / prior), the focal loss's usual initialisation (the
+        28,000 negatives of an image then start near zero loss)."""
+        if not 0.0 < prior < 1.0:
+            raise ValueError(f"prior must lie in (0, 1), got {prior}")
+        with torch.no_grad():
+            self.cls_heads[0].bias.fill_(-math.log((1.0 - prior) / prior))
+
+    def detection_loss(self, pooled, gt_boxes, image_size, loss_fn=None):
+        """The training loss of box_heads[0] / cls_heads[0] on the pooled trunk
+        features [B, 3136, 128] (``Plan.detector_features``) against gt_boxes
+        [B, G, 4]; ``loss_fn``: a ``DetectionLoss`` (default
+        hyper-parameters otherwise)."""
+        from ..losses.detection_loss import DetectionLoss
+        return (loss_fn or DetectionLoss())(self, pooled, gt_boxes, image_size)
 
     def forward(self, features, targets=None):
         """Reference :141-166: with training targets the last FPN level and the

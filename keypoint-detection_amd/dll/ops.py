@@ -22,6 +22,16 @@ and the train-mode BatchNorm2d + ReLU + Dropout2d that follows each of them
     y = bn_relu_dropout2d(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                           momentum=bn.momentum, eps=bn.eps, drop=mask)
     # == F.relu(F.batch_norm(x, rm, rv, w, b, True, momentum, eps)) * mask[:, :, None, None]
+
+and the person detector's training loss on the pooled trunk features (libkpd:
+kpd_detector_targets + kpd_detector_loss): anchor matching,
+focal + smooth-L1 loss and the closed-form gradients of box_heads[0] /
+cls_heads[0] in one fused pass:
+
+    from dll.ops import detector_loss
+    loss = detector_loss(plan.detector_features(image), box.weight, box.bias, cls.weight, cls.bias,
+                         person_head.anchors, gt_boxes, (H, W))
+    loss.backward()            # loss.cls_part / loss.box_part: the two parts, detached
 """
 from __future__ import annotations
 
@@ -117,3 +127,54 @@ def bn_relu_dropout2d(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Opt
         raise ValueError(f"drop must be [N, C] = {list(x.shape[:2])}, got {list(drop.shape)}")
     return BnReluDropout2dFunction.apply(x, weight, bias, running_mean, running_var, float(momentum), float(eps),
                                          bool(relu), drop)
+
+
+class DetectorLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pooled, box_weight, box_bias, cls_weight, cls_bias, anchors, gt_boxes, image_size, pos_thr,
+                neg_thr, tie_eps, alpha, gamma, beta, box_weight_factor):
+        assign, n_pos, _ = _native.detector_targets(anchors, gt_boxes, pooled.shape[0], image_size, pos_thr, neg_thr,
+                                                    tie_eps)
+        params = (box_weight, box_bias, cls_weight, cls_bias)
+        want = any(ctx.needs_input_grad[1:5])
+        loss, grads = _native.detector_loss(pooled, *params, anchors, gt_boxes, assign, n_pos, image_size, alpha,
+                                            gamma, beta, box_weight_factor, want_grad=want)
+        if want:   # the gradients of loss[0], in the parameters' own shapes and dtypes
+            ctx.save_for_backward(*[g.view_as(p).to(p.dtype) for g, p in zip(grads, params)])
+        ctx.mark_non_differentiable(assign, n_pos)
+        return loss[0], loss[1], loss[2], assign, n_pos
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, g_cls, g_box, _ga, _gn):
+        # the class and box parts are detached extras: only the total's gradient flows
+        grads = [g * g_loss if need else None for g, need in zip(ctx.saved_tensors, ctx.needs_input_grad[1:5])]
+        return (None, *grads) + (None,) * 10
+
+
+def detector_loss(pooled: torch.Tensor, box_weight: torch.Tensor, box_bias: torch.Tensor, cls_weight: torch.Tensor,
+                  cls_bias: torch.Tensor, anchors: torch.Tensor, gt_boxes: Optional[torch.Tensor], image_size, *,
+                  pos_thr: float = 0.5, neg_thr: float = 0.4, tie_eps: float = 1e-5, alpha: float = 0.25,
+                  gamma: float = 2.0, beta: float = 1.0 / 9, box_weight_factor: float = 1.0) -> torch.Tensor:
+    """The person detector's training loss on pooled
+    [B, 3136, 128] (``Plan.detector_features``) with gradients to the four
+    parameters of box_heads[0] / cls_heads[0] (their nn.Conv2d shapes
+    [36,128,1,1], [36], [9,128,1,1], [9]); nothing flows to ``pooled`` (the
+    trunk is frozen).  gt_boxes [B, G, 4] cxcywh normalised, G <= 64 (None or
+    G = 0: every anchor negative); image_size (H, W).  Returns the 0-d loss
+    (sum FL + box_weight_factor * sum SL1) / N with the detached extras
+    ``cls_part``, ``box_part`` (0-d), ``assign`` [B, 28224] int32 and ``n_pos``
+    [B] int32 as attributes.  Device tensors only; no host synchronisation."""
+    _native._require_cuda(pooled, "pooled")
+    for t, name in ((box_weight, "box_weight"), (box_bias, "box_bias"), (cls_weight, "cls_weight"),
+                    (cls_bias, "cls_bias"), (anchors, "anchors")):
+        _native._require_cuda(t, name)
+    if gt_boxes is not None:
+        _native._require_cuda(gt_boxes, "gt_boxes")
+    loss, cls_part, box_part, assign, n_pos = DetectorLossFunction.apply(
+        pooled, box_weight, box_bias, cls_weight, cls_bias, anchors, gt_boxes, tuple(int(v) for v in image_size),
+        float(pos_thr), float(neg_thr), float(tie_eps), float(alpha), float(gamma), float(beta),
+        float(box_weight_factor))
+    loss.cls_part, loss.box_part = cls_part.detach(), box_part.detach()
+    loss.assign, loss.n_pos = assign, n_pos
+    return loss

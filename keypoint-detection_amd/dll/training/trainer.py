@@ -27,9 +27,11 @@ and ``scaler`` is None -- the reference's f16 autocast needs its GradScaler,
 this does not.  Checkpoints hold fp32 state only: a run may switch between
 the two modes at any ``resume``.  Validation runs the eval head as always.
 
-Out of scope: training the trunk, the detector or KEYPOINT_HEAD,
-``torch.autocast`` / ``GradScaler`` integration, f16 training, AMP on a CPU
-device (raises), multi-GPU training.
+Out of scope: training the trunk or KEYPOINT_HEAD (the person detector has
+its own trainer, ``DetectorTrainer`` in detector_trainer.py, DESIGN.md §3j;
+joint detector + head steps are out of scope of both), ``torch.autocast`` /
+``GradScaler`` integration, f16 training, AMP on a CPU device (raises),
+multi-GPU training.
 """
 from __future__ import annotations
 

@@ -6,7 +6,8 @@ kpd_roi_features + kpd_roi_targets -> HeatmapHead train step -> checkpoints.
 
     python scripts/train.py --config configs/default_config.yaml --data_dir data/ \
         --output_dir runs/head [--model best_model.pth|synthetic] [--resume runs/head/checkpoint_epoch_5.pth] \
-        [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed] [--amp]
+        [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed] [--amp] \
+        [--train heatmap_head|detector]
 
 ``--model`` gives the starting weights (a checkpoint, or ``synthetic`` for the
 seeded synthetic state dict; default: the freshly initialised model);
@@ -17,6 +18,14 @@ validation epoch.  ``--amp`` trains in bf16 mixed precision
 master weights, no loss scaling); ``--precision`` is the plan's, for the trunk
 features and validation.  One JSON line per epoch goes to stdout: epoch, train_loss,
 loss (validation), avg_ADE, pck_*, learning_rate, steps, skipped_steps, seconds.
+
+``--train detector`` trains the person detector instead (``DetectorTrainer``,
+DESIGN.md §3j: kpd_detector_features -> anchor matching + focal / smooth-L1 loss
+-> step on ``person_detector.box_heads.0`` / ``cls_heads.0``), on the same
+dataset's boxes; its JSON line holds epoch, train_loss, loss, cls_loss,
+box_loss, recall_50, learning_rate, steps, skipped_steps, seconds, and its
+checkpoints load in predict.py / evaluate.py like any other.  ``--amp`` with it
+is an error: the step has no MFMA-bound part to speed up.
 Every argument is checked before the device is touched.
 """
 from __future__ import annotations
@@ -57,8 +66,12 @@ def parse_args(argv=None):
     ap.add_argument("--augment", action="store_true", help="augment the train split (also: augmentation.enabled)")
     ap.add_argument("--precision", default="split", choices=["split", "fp32", "mixed"])
     ap.add_argument("--amp", action="store_true", help="bf16 mixed-precision training (Trainer use_amp=True)")
+    ap.add_argument("--train", default="heatmap_head", choices=["heatmap_head", "detector"],
+                    help="what to train on the frozen trunk (default: the heatmap head)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
+    if args.train == "detector" and args.amp:
+        ap.error("--amp does not apply to --train detector: the step has no MFMA-bound part to speed up")
     for name in ("epochs", "batch_size", "max_steps"):
         v = getattr(args, name)
         if v is not None and v < 1:
@@ -84,7 +97,7 @@ def main(argv=None):
     import torch
 
     from dll.data import KeypointAugmentation, create_optimized_dataloader
-    from dll.training import Trainer
+    from dll.training import DetectorTrainer, Trainer
     from predict import load_config, load_model, setup_logging
     setup_logging()
     cfg = load_config(args.config)
@@ -108,7 +121,10 @@ def main(argv=None):
         model = _fresh_model(cfg, device, args.precision)
     else:
         model = load_model(args.model, cfg, device, args.precision)
-    trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp)
+    if args.train == "detector":
+        trainer = DetectorTrainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir)
+    else:
+        trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp)
     trainer.max_steps = args.max_steps
     if args.resume is not None:
         trainer.resume(args.resume)
