@@ -543,6 +543,35 @@ int kpd_adaptive_heatmap_loss(const float* pred, const float* gt, const float* t
                               float focal_alpha, float* loss_out, float* grad_pred, float* threshold_out,
                               void* stream);
 
+/* Training loss on the decoded keypoints: SpatialCoordinateLoss
+ * (dll/losses/keypoint_loss.py:117-199) of the soft-argmax decode of every
+ * plane, and its gradient with respect to the plane, in one pass.
+ * heat [planes][H][W] fp32; gt [planes][2] in the decode's normalised frame;
+ * vis [planes], a joint counts iff vis > 0 (all device).  Per plane
+ * p = softmax((h - max h) / temperature), e = (sum p x / (W-1), sum p y / (H-1)):
+ *   l = rho(e_x - g_x) + rho(e_y - g_y), d = |e - g|, f = clamp(d / distance_threshold, 1, 3)
+ *   loss[0] = sum over vis > 0 of pixel_weight_scale f l / (N_vis + 1e-8)
+ * rho: 0.5 z^2 for |z| < 1 else |z| - 0.5 (KPD_COORD_SMOOTH_L1, beta 1, and
+ * KPD_COORD_HUBER, delta 1); z^2 (KPD_COORD_MSE).  coords [planes][2] = e of
+ * every plane; grad (device [planes][H][W] or NULL) = d loss / d heat as torch
+ * autograd gives it (df/de = 0 outside the open band 1 < d/tau < 3).  A plane
+ * with vis <= 0 adds nothing and its gradient plane is zero by selection: its
+ * gt may be NaN.  H, W >= 2; temperature, distance_threshold > 0 and finite;
+ * planes = 0 writes loss 0.  Deterministic (integer count, fixed-order double
+ * sum); no floating-point atomics; no host synchronisation. */
+#define KPD_COORD_SMOOTH_L1 0
+#define KPD_COORD_MSE 1
+#define KPD_COORD_HUBER 2
+int kpd_coord_loss(const float* heat, const float* gt, const float* vis, int planes, int H, int W, float temperature,
+                   int loss_type, float pixel_weight_scale, float distance_threshold, float* coords, float* loss,
+                   float* grad, void* stream);
+
+/* The backward of the KPD_DECODE_SOFTARGMAX decode: grad_heat [planes][H][W]
+ * = sum over c of grad_coords[plane][c] d e_c / d heat, the same plane pass
+ * with the given seed. */
+int kpd_softargmax_backward(const float* heat, const float* grad_coords, int planes, int H, int W, float temperature,
+                            float* grad_heat, void* stream);
+
 /* Concurrency: a forward pass over B >= 32 images runs as min(n, B/16)
  * contiguous sub-batches on as many streams (forked from / joined back into
  * the caller's stream), so the latency-bound small launches of one sub-batch

@@ -36,7 +36,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
            "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features", "kpd_detector_features",
-           "kpd_detector_targets", "kpd_detector_loss")
+           "kpd_detector_targets", "kpd_detector_loss", "kpd_coord_loss", "kpd_softargmax_backward")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -73,6 +73,7 @@ BN_RELU = 1            # KPD_BN_RELU
 DET_ANCHORS = 28224    # KPD_DET_ANCHORS: 56 x 56 cells x 9 anchors, candidate order (i, j, a)
 DET_MAX_GT = 64        # KPD_DET_MAX_GT: ground-truth slots per image
 DECODE_ARGMAX, DECODE_SUBPIXEL, DECODE_SOFTARGMAX, DECODE_MODEL = 0, 1, 2, 3
+COORD_LOSS_TYPES = {"smooth_l1": 0, "mse": 1, "huber": 2}   # KPD_COORD_SMOOTH_L1 / _MSE / _HUBER
 STAGES = ("body", "fpn_lateral", "fpn0", "topk", "person_detect", "roi_align", "hm_attention", "hm_conv1",
           "hm_conv2", "hm_conv3", "hm_final_decode", "keypoint_head")
 
@@ -182,6 +183,8 @@ def load() -> ctypes.CDLL:
     lib.kpd_detector_targets.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     lib.kpd_detector_loss.argtypes = [c_void_p] * 9 + [c_int] * 4 + [c_float] * 4 + [c_void_p] * 6
+    lib.kpd_coord_loss.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_float, c_float] + [c_void_p] * 4
+    lib.kpd_softargmax_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
@@ -826,3 +829,56 @@ def adaptive_heatmap_loss(pred: torch.Tensor, gt: torch.Tensor, target_weight: O
                                                _ptr(loss), _ptr(grad), _ptr(thr), _stream(pred.device)),
               "kpd_adaptive_heatmap_loss")
     return loss, grad, thr
+
+
+def _coord_heat(heat: torch.Tensor, temperature: float):
+    """heat [n,K,H,W] as a contiguous fp32 device tensor; the checks shared by the two entries below
+    (made here so that they also hold for an empty tensor, which launches nothing)."""
+    heat = _dev_f32(heat.detach(), "heatmaps")
+    if heat.dim() != 4:
+        raise ValueError(f"expected [n, K, H, W] heatmaps, got {tuple(heat.shape)}")
+    if heat.size(2) < 2 or heat.size(3) < 2:
+        raise ValueError(f"the soft-argmax needs H, W >= 2, got {tuple(heat.shape[2:])}")
+    t = float(temperature)
+    if not (t > 0.0 and t < float("inf")):
+        raise ValueError(f"temperature must be positive and finite, got {temperature}")
+    return heat, t
+
+
+def coord_loss(heat: torch.Tensor, gt_coords: torch.Tensor, visibility: torch.Tensor, temperature: float,
+               loss_type: str, pixel_weight_scale: float, distance_threshold: float, want_grad: bool):
+    """kpd_coord_loss on heat [n,K,H,W], gt_coords [n,K,2], visibility [n,K]
+    (device tensors) -> (loss 0-d, coords [n,K,2], grad [n,K,H,W] or None).
+    No host synchronisation."""
+    heat, t = _coord_heat(heat, temperature)
+    if loss_type not in COORD_LOSS_TYPES:
+        raise ValueError(f"Unsupported loss type: {loss_type}")
+    n, K, H, W = heat.shape
+    dev = heat.device
+    gt = _dev_f32(gt_coords.detach(), "gt_coords").to(dev)
+    vis = _dev_f32(visibility.detach(), "visibility").to(dev)
+    if tuple(gt.shape) != (n, K, 2) or tuple(vis.shape) != (n, K):
+        raise ValueError(f"gt_coords must be [{n}, {K}, 2] and visibility [{n}, {K}], got {tuple(gt.shape)} and "
+                         f"{tuple(vis.shape)}")
+    coords = torch.empty(n, K, 2, device=dev)
+    loss = torch.empty((), device=dev)
+    grad = torch.empty_like(heat) if want_grad else None
+    with torch.cuda.device(dev):
+        check(load().kpd_coord_loss(_ptr(heat), _ptr(gt), _ptr(vis), n * K, H, W, t, COORD_LOSS_TYPES[loss_type],
+                                    float(pixel_weight_scale), float(distance_threshold), _ptr(coords), _ptr(loss),
+                                    _ptr(grad), _stream(dev)), "kpd_coord_loss")
+    return loss, coords, grad
+
+
+def softargmax_backward(heat: torch.Tensor, grad_coords: torch.Tensor, temperature: float) -> torch.Tensor:
+    """kpd_softargmax_backward: heat [n,K,H,W], grad_coords [n,K,2] -> d / d heat [n,K,H,W]."""
+    heat, t = _coord_heat(heat, temperature)
+    n, K, H, W = heat.shape
+    g = _dev_f32(grad_coords.detach(), "grad_coords").to(heat.device)
+    if tuple(g.shape) != (n, K, 2):
+        raise ValueError(f"grad_coords must be [{n}, {K}, 2], got {tuple(g.shape)}")
+    out = torch.empty_like(heat)
+    with torch.cuda.device(heat.device):
+        check(load().kpd_softargmax_backward(_ptr(heat), _ptr(g), n * K, H, W, t, _ptr(out), _stream(heat.device)),
+              "kpd_softargmax_backward")
+    return out

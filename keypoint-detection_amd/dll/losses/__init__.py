@@ -1,6 +1,6 @@
 from .detection_loss import DetectionLoss
 from .keypoint_loss import (AdaptiveHeatmapLoss, DynamicLossBalancer, ImprovedKeypointLoss, KeypointLoss, LossMetrics,
-                            SpatialCoordinateLoss)
+                            SoftArgmaxCoordinateLoss, SpatialCoordinateLoss)
 
 __all__ = ["AdaptiveHeatmapLoss", "DetectionLoss", "DynamicLossBalancer", "ImprovedKeypointLoss", "KeypointLoss",
-           "LossMetrics", "SpatialCoordinateLoss"]
+           "LossMetrics", "SoftArgmaxCoordinateLoss", "SpatialCoordinateLoss"]

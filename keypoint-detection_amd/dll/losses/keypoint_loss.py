@@ -160,6 +160,41 @@ class SpatialCoordinateLoss(nn.Module):
         return per_kpt.sum() / (mask.sum() + 1e-8)
 
 
+class SoftArgmaxCoordinateLoss(nn.Module):
+    """``SpatialCoordinateLoss`` of the soft-argmax decode of the heatmaps --
+    the coordinate term as a training loss on ``outputs["keypoints"]`` -- on
+    the device in one native pass with its gradient (``kpd_coord_loss``,
+    DESIGN.md §3k; not in the reference, which reaches it through autograd).
+    ``forward(heatmaps [n,K,H,W], gt_coords [n,K,2], visibility [n,K]) ->
+    loss``; ``gt_coords`` in the decode's frame (pixel i of a W-wide map is
+    i / (W-1)), joints with visibility <= 0 dropped by selection (their
+    gt_coords may be NaN).  No host synchronisation; without a visible joint
+    the loss and the gradient are 0.  ``last_coords`` holds the last call's
+    decoded [n,K,2] (detached).  There is no CPU path: CPU tensors raise."""
+
+    def __init__(self, temperature: float = 1.0, loss_type: str = "smooth_l1", pixel_weight_scale: float = 100.0,
+                 distance_threshold: float = 5.0):
+        super().__init__()
+        if loss_type not in _native.COORD_LOSS_TYPES:
+            raise ValueError(f"Unsupported loss type: {loss_type}")
+        if not (0.0 < float(temperature) < float("inf")):
+            raise ValueError(f"temperature must be positive and finite, got {temperature}")
+        if not (0.0 < float(distance_threshold) < float("inf")):
+            raise ValueError(f"distance_threshold must be positive and finite, got {distance_threshold}")
+        self.temperature = float(temperature)
+        self.loss_type = loss_type
+        self.pixel_weight_scale = float(pixel_weight_scale)
+        self.distance_threshold = float(distance_threshold)
+        self.last_coords: Optional[torch.Tensor] = None
+
+    def forward(self, heatmaps: torch.Tensor, gt_coords: torch.Tensor, visibility: torch.Tensor) -> torch.Tensor:
+        from ..ops import soft_argmax_coord_loss
+        loss, self.last_coords = soft_argmax_coord_loss(heatmaps, gt_coords, visibility, self.temperature,
+                                                        self.loss_type, self.pixel_weight_scale,
+                                                        self.distance_threshold)
+        return loss
+
+
 class ImprovedKeypointLoss(nn.Module):
     """Heatmap + coordinate + visibility loss with dynamic weights (reference
     :283-389).  ``forward(predictions, targets) -> (total, loss_dict)``;

@@ -32,6 +32,15 @@ cls_heads[0] in one fused pass:
     loss = detector_loss(plan.detector_features(image), box.weight, box.bias, cls.weight, cls.bias,
                          person_head.anchors, gt_boxes, (H, W))
     loss.backward()            # loss.cls_part / loss.box_part: the two parts, detached
+
+and the coordinate term on the decoded keypoints (libkpd: kpd_coord_loss /
+kpd_softargmax_backward): the soft-argmax decode as a
+differentiable op, and SpatialCoordinateLoss of it with the gradient onto the
+heatmaps in the same pass:
+
+    from dll.ops import soft_argmax, soft_argmax_coord_loss
+    coords = soft_argmax(heat, temperature=1.0)                  # == decode_heatmaps_soft_argmax(heat)[0]
+    loss, coords = soft_argmax_coord_loss(heat, gt_coords, visibility)
 """
 from __future__ import annotations
 
@@ -178,3 +187,61 @@ def detector_loss(pooled: torch.Tensor, box_weight: torch.Tensor, box_bias: torc
     loss.cls_part, loss.box_part = cls_part.detach(), box_part.detach()
     loss.assign, loss.n_pos = assign, n_pos
     return loss
+
+
+class SoftArgmaxFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, heat: torch.Tensor, temperature: float):
+        ctx.save_for_backward(heat)
+        ctx.temperature = temperature
+        return _native.decode_heatmaps(heat, _native.DECODE_SOFTARGMAX, temperature)[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_coords: torch.Tensor):
+        (heat,) = ctx.saved_tensors
+        return _native.softargmax_backward(heat, grad_coords, ctx.temperature).to(heat.dtype), None
+
+
+def soft_argmax(heat: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+    """The soft-argmax decode of heat [n, K, H, W] -> coords [n, K, 2]
+    (normalised x, y), differentiable with respect to ``heat``: the forward is
+    ``decode_heatmaps_soft_argmax``'s (kpd_decode_heatmaps, bit for bit), the
+    backward kpd_softargmax_backward."""
+    _native._coord_heat(heat, temperature)   # shape, device and temperature checks before any launch
+    return SoftArgmaxFunction.apply(heat, float(temperature))
+
+
+class SoftArgmaxCoordLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, heat, gt_coords, visibility, temperature, loss_type, pixel_weight_scale, distance_threshold):
+        loss, coords, grad = _native.coord_loss(heat, gt_coords, visibility, temperature, loss_type,
+                                                pixel_weight_scale, distance_threshold,
+                                                want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0, device=heat.device))
+        ctx.heat_dtype = heat.dtype
+        ctx.mark_non_differentiable(coords)
+        return loss.to(heat.dtype), coords
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _g_coords):
+        (grad,) = ctx.saved_tensors
+        if grad.numel() == 0:
+            return (None,) * 7
+        return (grad * g_loss).to(ctx.heat_dtype), None, None, None, None, None, None
+
+
+def soft_argmax_coord_loss(heat: torch.Tensor, gt_coords: torch.Tensor, visibility: torch.Tensor,
+                           temperature: float = 1.0, loss_type: str = "smooth_l1", pixel_weight_scale: float = 100.0,
+                           distance_threshold: float = 5.0):
+    """``SpatialCoordinateLoss`` of the soft-argmax decode of heat [n, K, H, W]
+    against gt_coords [n, K, 2] (the decode's normalised frame) over the joints
+    with visibility [n, K] > 0, in one native pass (kpd_coord_loss, DESIGN.md
+    §3k) -> (loss 0-d, coords [n, K, 2]).  The gradient with respect to
+    ``heat`` is computed in the forward when ``heat.requires_grad``; ``coords``
+    is detached (use ``soft_argmax`` for a differentiable decode).  A masked
+    joint's gt may hold anything, NaN included.  Device tensors only; no host
+    synchronisation."""
+    return SoftArgmaxCoordLossFunction.apply(heat, gt_coords, visibility, float(temperature), str(loss_type),
+                                             float(pixel_weight_scale), float(distance_threshold))

@@ -7,6 +7,7 @@ driving the native pieces of a top-down training step:
     x      = plan.roi_features(image, boxes, rows)            kpd_roi_features, no_grad
     gt, tw = generate_roi_targets(keypoints, vis, boxes, rows)   kpd_roi_targets
     loss   = model.loss_fn.heatmap_loss(head(x)[0], gt, tw)   head.train(): native fwd + bwd
+    loss  += coord_weight * coord_loss(heat, joints in the ROI frame, tw)   coord_weight > 0: kpd_coord_loss
     loss.backward(); optimizer.step()
 
 Only ``model.heatmap_head`` is trained: the optimizer holds its parameters and
@@ -27,8 +28,27 @@ and ``scaler`` is None -- the reference's f16 autocast needs its GradScaler,
 this does not.  Checkpoints hold fp32 state only: a run may switch between
 the two modes at any ``resume``.  Validation runs the eval head as always.
 
-Out of scope: training the trunk or KEYPOINT_HEAD (the person detector has
-its own trainer, ``DetectorTrainer`` in detector_trainer.py, DESIGN.md §3j;
+``coord_weight > 0`` adds the coordinate term on the decoded keypoints
+(DESIGN.md §3k): ``SpatialCoordinateLoss`` (smooth-L1, scale 100, threshold 5:
+the reference's ImprovedKeypointLoss defaults) of the soft-argmax decode of the
+train-mode heatmaps at ``coord_temperature`` -- 1.0, the default, is the eval
+forward's own decode, so the term supervises what ``outputs["keypoints"]``
+returns -- against each person's joints in their own ROI frame, masked by the
+per-joint weight of the heatmap targets, so unlabelled joints, joints outside
+their box and padding boxes drop out of both terms alike.  The step's loss is
+``heatmap_loss + coord_weight * coord_loss`` with a fixed weight (the
+reference's DynamicLossBalancer reads every component on the host each step;
+the step keeps its one synchronisation).  Validation then also reports
+``coord_loss`` and ``avg_ADE_soft``, the ADE of that soft-argmax decode.  With
+``coord_weight == 0`` (default) none of this runs: steps, history keys and
+checkpoints are what they were.  Whether the term improves trained accuracy,
+and at which weight or temperature, is unmeasured: no dataset run exists.
+
+Out of scope: the visibility term (the head's visibility is a threshold on the
+map's maximum and has no gradient), DynamicLossBalancer, coordinate
+supervision of the detector or KEYPOINT_HEAD, training the trunk or
+KEYPOINT_HEAD (the person detector has its own trainer, ``DetectorTrainer``
+in detector_trainer.py, DESIGN.md §3j;
 joint detector + head steps are out of scope of both), ``torch.autocast`` /
 ``GradScaler`` integration, f16 training, AMP on a CPU device (raises),
 multi-GPU training.
@@ -45,6 +65,7 @@ import torch.nn as nn
 from torch.optim import lr_scheduler
 
 from ..configs.training_config import TrainingConfig
+from ..losses.keypoint_loss import SoftArgmaxCoordinateLoss
 from ..models.heatmap_head import decode_heatmaps, generate_roi_targets
 from ..utils.metric import _metrics_on_device
 
@@ -65,7 +86,12 @@ def batch_boxes(batch: Dict) -> torch.Tensor:
 
 class Trainer:
     def __init__(self, model: nn.Module, device: torch.device, train_dataloader, val_dataloader,
-                 config: TrainingConfig, output_dir: Optional[Union[str, Path]] = None, use_amp: bool = False):
+                 config: TrainingConfig, output_dir: Optional[Union[str, Path]] = None, use_amp: bool = False,
+                 coord_weight: float = 0.0, coord_temperature: float = 1.0):
+        if not (0.0 <= float(coord_weight) < float("inf")):
+            raise ValueError(f"coord_weight must be finite and >= 0, got {coord_weight}")
+        if not (0.0 < float(coord_temperature) < float("inf")):
+            raise ValueError(f"coord_temperature must be positive and finite, got {coord_temperature}")
         if use_amp and torch.device(device).type != "cuda":
             raise NotImplementedError("AMP training runs on the native bf16 kernels of the heatmap head's train path "
                                       "(DESIGN.md §3i), which need a GPU device; construct the Trainer with "
@@ -85,6 +111,10 @@ class Trainer:
         self.use_amp = bool(use_amp)
         self.scaler = None
         self.head.train_precision = "mixed" if self.use_amp else "split"
+        # the coordinate term on the decoded keypoints (module docstring); 0: never built, never launched
+        self.coord_weight = float(coord_weight)
+        self.coord_temperature = float(coord_temperature)
+        self.coord_loss_fn = SoftArgmaxCoordinateLoss(self.coord_temperature) if self.coord_weight > 0 else None
         self.model.eval()
         self.optimizer = self._create_optimizer()
         sc = config.lr_scheduler
@@ -139,21 +169,35 @@ class Trainer:
         gt, tw = generate_roi_targets(kp, vis, boxes, rows, tuple(x.shape[2:]), TARGET_SIGMA)
         return x, gt, tw, rows, boxes
 
+    def _roi_joints(self, batch: Dict, rows: torch.Tensor, boxes: torch.Tensor, K: int):
+        """Each person's joints [n,K,2] in their own ROI's frame, (kp - (c - wh/2)) / wh: the inverse of
+        validate_epoch's mapping.  An empty side gives inf / NaN, which the target weight of that ROI (0)
+        masks.  Device indexing, no host synchronisation."""
+        kp = batch["keypoints"].to(self.device, torch.float32).reshape(-1, K, 2)[rows.long()]
+        b = boxes.view(-1, 4)[rows.long()].unsqueeze(1)
+        return (kp - (b[..., :2] - b[..., 2:] / 2)) / b[..., 2:]
+
     def train_step(self, batch: Dict) -> Dict:
         """One optimizer step on a collated batch: {'loss': 0-d device tensor
-        (detached), 'rows': n, 'skipped': bool}.  A batch without a labelled
-        box is skipped (no step, loss None)."""
+        (detached), 'rows': n, 'skipped': bool}; with coord_weight > 0 'loss'
+        is the total and 'heatmap_loss' / 'coord_loss' its two parts.  A batch
+        without a labelled box is skipped (no step, loss None)."""
         ft = self._features_and_targets(batch)
         if ft is None:
             return {"loss": None, "rows": 0, "skipped": True}
-        x, gt, tw, rows, _ = ft
+        x, gt, tw, rows, boxes = ft
         self.head.train()
         self.optimizer.zero_grad(set_to_none=True)
         heat = self.head(x)[0]
         loss = self.model.loss_fn.heatmap_loss(heat, gt, tw)
+        parts = {}
+        if self.coord_loss_fn is not None:
+            coord = self.coord_loss_fn(heat, self._roi_joints(batch, rows, boxes, heat.size(1)), tw)
+            parts = {"heatmap_loss": loss.detach(), "coord_loss": coord.detach()}
+            loss = loss + self.coord_weight * coord
         loss.backward()
         self.optimizer.step()
-        return {"loss": loss.detach(), "rows": int(rows.numel()), "skipped": False}
+        return {"loss": loss.detach(), "rows": int(rows.numel()), "skipped": False, **parts}
 
     def train_epoch(self) -> Dict[str, float]:
         self._plan = None
@@ -179,10 +223,15 @@ class Trainer:
         """Mean loss, ADE and PCK over the validation batches with a labelled
         box: the head in eval mode through its own plan on the same features
         and targets; the heatmaps argmax-decoded and mapped to image
-        coordinates through the unclamped box, against the labelled joints."""
+        coordinates through the unclamped box, against the labelled joints.
+        With coord_weight > 0 also the coordinate term (``coord_loss``; ``loss``
+        stays the heatmap term) and ``avg_ADE_soft``, the ADE of the soft-argmax
+        decode at coord_temperature."""
         self._plan = None
         self.model.eval()
         names = ["loss", "avg_ADE"] + [f"pck_{t}" for t in self.config.pck_thresholds]
+        if self.coord_loss_fn is not None:
+            names += ["coord_loss", "avg_ADE_soft"]
         sums, n = dict.fromkeys(names, 0.0), 0
         with torch.no_grad():
             for batch in self.val_dataloader:
@@ -201,6 +250,10 @@ class Trainer:
                 want = batch["keypoints"].to(self.device, torch.float32).reshape(-1, K, 2)[rows.long()]
                 vis = batch["visibilities"].to(self.device, torch.float32).reshape(-1, K)[rows.long()]
                 vals = _metrics_on_device(pred, want, vis, self.pck_thresholds)
+                if self.coord_loss_fn is not None:
+                    coord = self.coord_loss_fn(heat, self._roi_joints(batch, rows, boxes, K), tw)
+                    soft = self.coord_loss_fn.last_coords * b[..., 2:] + (b[..., :2] - b[..., 2:] / 2)
+                    vals = vals + [float(coord), _metrics_on_device(soft, want, vis, self.pck_thresholds)[0]]
                 for name, v in zip(names, [float(loss)] + vals):
                     sums[name] += float(v)
                 n += 1
@@ -241,6 +294,7 @@ class Trainer:
         line = {"epoch": int(epoch), "train_loss": float(train["loss"]), "loss": float(val["loss"]),
                 "avg_ADE": float(val["avg_ADE"])}
         line.update({k: float(v) for k, v in val.items() if k.startswith("pck_")})
+        line.update({k: float(val[k]) for k in ("coord_loss", "avg_ADE_soft") if k in val})
         line.update({"learning_rate": float(lr), "steps": int(train["steps"]),
                      "skipped_steps": int(train["skipped_steps"]), "seconds": float(seconds)})
         for k, v in line.items():
@@ -266,8 +320,10 @@ class Trainer:
                 self.best_val_loss = val["loss"]
             interval = max(1, int(self.config.checkpoint_interval))
             self.save_checkpoint(epoch, is_best=is_best, periodic=epoch % interval == 0)
-            logger.info("epoch %d: train loss %.6f  val loss %.6f  ADE %.5f  lr %.2e", epoch, train["loss"],
-                        val["loss"], val["avg_ADE"], lr)
+            soft = "  coord loss %.6f  soft ADE %.5f" % (val["coord_loss"], val["avg_ADE_soft"]) \
+                if "coord_loss" in val else ""
+            logger.info("epoch %d: train loss %.6f  val loss %.6f  ADE %.5f%s  lr %.2e", epoch, train["loss"],
+                        val["loss"], val["avg_ADE"], soft, lr)
             if on_epoch is not None:
                 on_epoch(line)
         return self.model, self.history

@@ -7,7 +7,7 @@ kpd_roi_features + kpd_roi_targets -> HeatmapHead train step -> checkpoints.
     python scripts/train.py --config configs/default_config.yaml --data_dir data/ \
         --output_dir runs/head [--model best_model.pth|synthetic] [--resume runs/head/checkpoint_epoch_5.pth] \
         [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed] [--amp] \
-        [--train heatmap_head|detector]
+        [--train heatmap_head|detector] [--coord-weight W] [--coord-temperature T]
 
 ``--model`` gives the starting weights (a checkpoint, or ``synthetic`` for the
 seeded synthetic state dict; default: the freshly initialised model);
@@ -18,6 +18,10 @@ validation epoch.  ``--amp`` trains in bf16 mixed precision
 master weights, no loss scaling); ``--precision`` is the plan's, for the trunk
 features and validation.  One JSON line per epoch goes to stdout: epoch, train_loss,
 loss (validation), avg_ADE, pck_*, learning_rate, steps, skipped_steps, seconds.
+``--coord-weight W`` (W > 0) adds W x the coordinate loss of the soft-argmax
+decoded keypoints to every step (``Trainer(coord_weight=W)``, DESIGN.md §3k);
+the line then also holds coord_loss and avg_ADE_soft (validation).  It is an
+error with ``--train detector``.
 
 ``--train detector`` trains the person detector instead (``DetectorTrainer``,
 DESIGN.md §3j: kpd_detector_features -> anchor matching + focal / smooth-L1 loss
@@ -66,12 +70,22 @@ def parse_args(argv=None):
     ap.add_argument("--augment", action="store_true", help="augment the train split (also: augmentation.enabled)")
     ap.add_argument("--precision", default="split", choices=["split", "fp32", "mixed"])
     ap.add_argument("--amp", action="store_true", help="bf16 mixed-precision training (Trainer use_amp=True)")
+    ap.add_argument("--coord-weight", type=float, default=0.0,
+                    help="weight of the coordinate term on the soft-argmax decoded keypoints (0: off)")
+    ap.add_argument("--coord-temperature", type=float, default=1.0,
+                    help="soft-argmax temperature of that term (1.0: the eval forward's decode)")
     ap.add_argument("--train", default="heatmap_head", choices=["heatmap_head", "detector"],
                     help="what to train on the frozen trunk (default: the heatmap head)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     if args.train == "detector" and args.amp:
         ap.error("--amp does not apply to --train detector: the step has no MFMA-bound part to speed up")
+    if not (0.0 <= args.coord_weight < float("inf")):
+        ap.error("--coord-weight must be finite and >= 0")
+    if not (0.0 < args.coord_temperature < float("inf")):
+        ap.error("--coord-temperature must be positive and finite")
+    if args.train == "detector" and args.coord_weight > 0:
+        ap.error("--coord-weight does not apply to --train detector: the detector has no keypoint output")
     for name in ("epochs", "batch_size", "max_steps"):
         v = getattr(args, name)
         if v is not None and v < 1:
@@ -124,7 +138,8 @@ def main(argv=None):
     if args.train == "detector":
         trainer = DetectorTrainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir)
     else:
-        trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp)
+        trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp,
+                          coord_weight=args.coord_weight, coord_temperature=args.coord_temperature)
     trainer.max_steps = args.max_steps
     if args.resume is not None:
         trainer.resume(args.resume)
