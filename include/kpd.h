@@ -267,9 +267,11 @@ int kpd_draw_poses(uint8_t* const* images, const int* heights, const int* widths
  * (dll/models/heatmap_head.py:163-224).  kpts: [planes][2] normalised (x, y)
  * (device), out: [planes][H][W] fp32 (device); the (6*int(sigma)+1)^2
  * normalised Gaussian is centred at (floor(x*W), floor(y*H)) and cropped;
- * keypoints outside [0,1) leave their plane zero.  Synchronises the stream
- * (the kernel table is staged from host memory). */
-int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, float sigma, float* out, void* stream);
+ * keypoints outside [0,1) leave their plane zero.  sigma is the reference's
+ * Python double: the kernel size takes int() of it unrounded and 2*sigma^2 is
+ * rounded to fp32 once.  Synchronises the stream (the kernel table is staged
+ * from host memory). */
+int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, double sigma, float* out, void* stream);
 
 /* Per-ROI training targets of the top-down HeatmapHead: the
  * person's own joints placed in the frame the head predicts in, by the
@@ -687,7 +689,13 @@ int kpd_roi_features(kpd_plan* plan, const float* image, int B, int C, int H, in
 /* ChannelAttention.forward (keypoint_model.py:33-44) on x [B][128][H][W] ->
  * scores [B][128] (sigmoid); select_top_k_channels (:653-661): topk [B][k]
  * int32 (descending score, ties to the lower index) and selected
- * [B][k][H][W] = x[b, topk[b]] (both nullable).  k = 64. */
+ * [B][k][H][W] = x[b, topk[b]] (both nullable).  k = 64.
+ * Non-finite input follows torch: the order is total, a NaN score ranks
+ * before every number (index ascending among NaNs), so topk[b] always holds
+ * k distinct indices in [0, 128).  The ReLU of the FC keeps a NaN, so a NaN
+ * anywhere in image b (its channel mean is NaN, and every hidden unit reads
+ * every channel) makes all 128 scores of b NaN and topk[b] = 0 .. k-1; an
+ * infinity gives the scores IEEE arithmetic gives (inf - inf = NaN). */
 int kpd_channel_attention(kpd_plan* plan, const float* x, int B, int C, int H, int W, float* scores, int32_t* topk,
                           int k, float* selected, void* stream);
 
@@ -697,7 +705,15 @@ int kpd_channel_attention(kpd_plan* plan, const float* x, int B, int C, int H, i
  *   KPD_DECODE_SOFTARGMAX decode_heatmaps_soft_argmax (:372-413), param = temperature
  *   KPD_DECODE_MODEL      MultiPersonKeypointModel.decode_heatmap (keypoint_model.py:250-313):
  *                         soft-argmax + 3-class visibility vis [planes][3]
- * keypoints [planes][2] normalised, scores [planes] (the maximum; nullable). */
+ * keypoints [planes][2] normalised, scores [planes] (the maximum; nullable).
+ * Edges, as torch has them: the maximum is torch.max's (first index on ties,
+ * a NaN counts as the maximum, the first NaN wins; an all -inf plane gives
+ * index 0); a sub-pixel window whose mass is not positive (zero, negative,
+ * NaN) or that is empty (negative window size: pad = floor(w / 2) < 0) gives
+ * zeros; soft-argmax divides by any non-zero temperature (0 is rejected with
+ * KPD_EHIP before a launch), and a NaN in the plane or an all -inf plane
+ * gives NaN coordinates, as softmax does; a NaN maximum is visibility class 2
+ * (it fails both comparisons).  H, W >= 2. */
 #define KPD_DECODE_ARGMAX 0
 #define KPD_DECODE_SUBPIXEL 1
 #define KPD_DECODE_SOFTARGMAX 2
@@ -707,7 +723,9 @@ int kpd_decode_heatmaps(const float* heat, int planes, int H, int W, int mode, f
 
 /* torchvision.ops.roi_align as extract_roi_features calls it
  * (keypoint_model.py:212-228): features [B][C][H][W], rois [R][5] =
- * (batch index, x1, y1, x2, y2) -> out [R][C][out_h][out_w]. */
+ * (batch index, x1, y1, x2, y2) -> out [R][C][out_h][out_w].  The batch
+ * index is truncated towards zero as torchvision does; a ROI whose index does
+ * not name one of the B images (or is NaN) reads nothing and gives zeros. */
 int kpd_roi_align(const float* features, int B, int C, int H, int W, const float* rois, int R, int out_h, int out_w,
                   float spatial_scale, int sampling_ratio, int aligned, float* out, void* stream);
 

@@ -94,18 +94,21 @@ __global__ __launch_bounds__(kMetricThreads) void keypoint_metrics_kernel(const 
 
 }  // namespace
 
-extern "C" int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, float sigma, float* out,
+extern "C" int kpd_target_heatmaps(const float* kpts, int planes, int H, int W, double sigma, float* out,
                                    void* stream) {
-  if (!out || (planes > 0 && !kpts) || planes < 0 || H <= 0 || W <= 0 || !(sigma > 0.f) || sigma > 64.f)
+  if ((planes > 0 && (!kpts || !out)) || planes < 0 || H <= 0 || W <= 0 || !(sigma > 0.0) || sigma > 64.0)
     return kpd_fail_einval("kpd_target_heatmaps: bad arguments");
   if (planes == 0) return KPD_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // get_gaussian_kernel(6*int(sigma)+1, sigma) in fp32: coords i - (ks-1)/2,
   // exp(-(cy^2 + cx^2) / (2 sigma^2)), divided by its sum (summed in double,
-  // rounded once).
+  // rounded once).  sigma is the reference's Python double: int() truncates
+  // it unrounded (2.9999999 -> 13 x 13, not float's 3.0 -> 19 x 19), and the
+  // denominator 2 * sigma ** 2 is rounded to fp32 once, as torch does with a
+  // Python scalar.
   const int ks = 6 * (int)sigma + 1;
   std::vector<float> g((size_t)ks * ks);
-  const float den = (float)(2.0 * (double)sigma * (double)sigma);
+  const float den = (float)(2.0 * (sigma * sigma));
   double sum = 0.0;
   for (int a = 0; a < ks; ++a)
     for (int b = 0; b < ks; ++b) {

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sta
     float a = b0[j];
 #pragma unroll 32
     for (int k = 0; k < FC; ++k) a = fmaf(sw0[j * FC + k], vv[k], a);
-    h[c] = fmaxf(a, 0.f);
+    h[c] = a <= 0.f ? 0.f : a;   // torch's ReLU: a NaN stays (fmaxf would drop it)
   }
   __syncthreads();
   if (c >= FC) {
@@ -111,14 +111,18 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sta
     om = fmaf(sw2[c * 8 + j], h[8 + j], om);
   }
   const float score = kpd_sigmoid(oa + om);
-  sc[c] = score;
+  // the ranking key makes the order total: a NaN score ranks before every
+  // number (torch.topk), so the ranks stay a permutation of 0..127 and every
+  // slot of topk is written; a sigmoid never reaches +inf by itself
+  const float key = score != score ? INFINITY : score;
+  sc[c] = key;
   __syncthreads();   // waves 2-3 (c >= 128) have exited: the barrier counts waves 0-1
-  // rank = number of channels ordered before c (score desc, index asc on ties)
+  // rank = number of channels ordered before c (key desc, index asc on ties)
   int rank = 0;
 #pragma unroll 32
   for (int k = 0; k < FC; ++k) {
     const float o = sc[k];
-    rank += (o > score) || (o == score && k < c);
+    rank += (o > key) || (o == key && k < c);
   }
   if (rank < TOPK) topk[n * TOPK + rank] = c;
   if (scores_out) scores_out[n * FC + c] = score;

@@ -496,8 +496,8 @@ inline void kpd_path_at(unsigned site, int idx = -1) {
 // mode: KPD_DECODE_* (include/kpd.h)
 hipError_t launch_decode_planes(const float* heat, int planes, int H, int W, int mode, float param, float* kpts,
                                 float* scores, float* vis, hipStream_t st);
-hipError_t launch_roi_align_nchw(const float* feat, int C, int H, int W, const float* rois, int R, int oh, int ow,
-                                 float scale, int sr, int aligned, float* out, hipStream_t st);
+hipError_t launch_roi_align_nchw(const float* feat, int B, int C, int H, int W, const float* rois, int R, int oh,
+                                 int ow, float scale, int sr, int aligned, float* out, hipStream_t st);
 hipError_t launch_nchw_rows_to_nhwc(const float* in, int N, int C, int H, int W, float* out, float* stats,
                                     hipStream_t st, float* amax = nullptr, int amax_stride = 0);
 hipError_t launch_nhwc_to_nchw(const float* in, int N, int HW, int C, float* out, hipStream_t st);

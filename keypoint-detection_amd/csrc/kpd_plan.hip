@@ -1809,7 +1809,7 @@ int kpd_roi_align(const float* feat, int B, int C, int H, int W, const float* ro
                   float spatial_scale, int sampling_ratio, int aligned, float* out, void* stream) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || R < 0 || out_h <= 0 || out_w <= 0 || (R > 0 && (!feat || !rois || !out)))
     return fail(KPD_EINVAL, "bad roi_align arguments");
-  HIP_TRY(launch_roi_align_nchw(feat, C, H, W, rois, R, out_h, out_w, spatial_scale, sampling_ratio, aligned, out,
+  HIP_TRY(launch_roi_align_nchw(feat, B, C, H, W, rois, R, out_h, out_w, spatial_scale, sampling_ratio, aligned, out,
                                 reinterpret_cast<hipStream_t>(stream)));
   return KPD_OK;
 }

@@ -139,15 +139,26 @@ __global__ __launch_bounds__(DT) void decode_planes_kernel(const float* __restri
 
 // torchvision roi_align (CPU/CUDA reference semantics), NCHW features,
 // rois [R][5] = (batch index, x1, y1, x2, y2) in input coordinates.  One
-// thread per output element; samples summed in (iy, ix) order, / count.
-__global__ __launch_bounds__(256) void roi_align_nchw_kernel(const float* __restrict__ feat, int C, int H, int W,
-                                                             const float* __restrict__ rois, int R, int oh, int ow,
-                                                             float scale, int sr, int aligned, float* __restrict__ out) {
+// thread per output element; samples summed in (iy, ix) order, / count.  A
+// ROI whose batch index is not in [0, B) (a NaN included) reads nothing and
+// gives zeros.
+__global__ __launch_bounds__(256) void roi_align_nchw_kernel(const float* __restrict__ feat, int B, int C, int H,
+                                                             int W, const float* __restrict__ rois, int R, int oh,
+                                                             int ow, float scale, int sr, int aligned,
+                                                             float* __restrict__ out) {
+  // torchvision's expressions as written, each operation rounded: a fused
+  // multiply-add would move a sample coordinate by an ulp, which at |x| ~ W
+  // is more than the whole rounding budget of a bin (and can flip a skip test)
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * 256 + threadIdx.x, total = (long)R * C * oh * ow;
   if (idx >= total) return;
   const int pw = (int)(idx % ow), ph = (int)((idx / ow) % oh), c = (int)((idx / ((long)ow * oh)) % C);
   const int r = (int)(idx / ((long)ow * oh * C));
   const float* ro = rois + (size_t)r * 5;
+  if (!(ro[0] > -1.f && ro[0] < (float)B)) {   // (int) truncates towards zero: (-1, B) names images 0 .. B-1
+    out[idx] = 0.f;
+    return;
+  }
   const int b = (int)ro[0];
   const float off = aligned ? 0.5f : 0.f;
   const float x1 = ro[1] * scale - off, y1 = ro[2] * scale - off, x2 = ro[3] * scale - off, y2 = ro[4] * scale - off;
@@ -388,12 +399,12 @@ hipError_t launch_decode_planes(const float* heat, int planes, int H, int W, int
   return hipGetLastError();
 }
 
-hipError_t launch_roi_align_nchw(const float* feat, int C, int H, int W, const float* rois, int R, int oh, int ow,
-                                 float scale, int sr, int aligned, float* out, hipStream_t st) {
+hipError_t launch_roi_align_nchw(const float* feat, int B, int C, int H, int W, const float* rois, int R, int oh,
+                                 int ow, float scale, int sr, int aligned, float* out, hipStream_t st) {
   const long total = (long)R * C * oh * ow;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(roi_align_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, C, H, W,
-                     rois, R, oh, ow, scale, sr, aligned, out);
+  hipLaunchKernelGGL(roi_align_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, B, C, H,
+                     W, rois, R, oh, ow, scale, sr, aligned, out);
   return hipGetLastError();
 }
 

@@ -121,7 +121,7 @@ def load() -> ctypes.CDLL:
                                           ctypes.POINTER(c_int)]
     lib.kpd_plan_path_log.argtypes = [c_void_p, c_int]
     lib.kpd_plan_path_query.argtypes = [c_void_p, c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    lib.kpd_target_heatmaps.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]
+    lib.kpd_target_heatmaps.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]
     lib.kpd_keypoint_metrics.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_float),
                                          c_int, c_void_p, c_void_p]
     lib.kpd_preprocess_batch.argtypes = [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int),

@@ -242,7 +242,7 @@ def generate_target_heatmap(keypoints: torch.Tensor, heatmap_size: Tuple[int, in
     out = torch.empty(B, K, H, W, device=kp.device, dtype=torch.float32)
     lib = _native.load()
     with torch.cuda.device(kp.device):
-        rc = lib.kpd_target_heatmaps(_native._ptr(kp), B * K, H, W, ctypes.c_float(sigma), _native._ptr(out),
+        rc = lib.kpd_target_heatmaps(_native._ptr(kp), B * K, H, W, ctypes.c_double(sigma), _native._ptr(out),
                                      _native._stream(kp.device))
     _native.check(rc, "kpd_target_heatmaps")
     return out

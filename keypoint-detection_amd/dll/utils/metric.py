@@ -39,6 +39,9 @@ def _metrics_on_device(pred: torch.Tensor, gt: torch.Tensor, vis: torch.Tensor, 
     p = pred.float().contiguous()
     g = gt.to(dev).float().contiguous()
     v = vis.to(dev).float().contiguous()
+    if len(thresholds) > 16:
+        # not a data error to log and answer with zeros: the kernel's limit
+        raise _native.KpdNativeError(f"kpd_keypoint_metrics takes at most 16 PCK thresholds, got {len(thresholds)}")
     if v.numel() != p.numel() // 2:
         raise ValueError(f"visibilities {tuple(vis.shape)} do not match keypoints {tuple(pred.shape)}")
     out = torch.empty(1 + len(thresholds), device=dev, dtype=torch.float32)
