@@ -539,7 +539,9 @@ int kpd_augment_batch(const uint8_t* const* srcs, const int* heights, const int*
  * torch's fp32 rank / lerp), else 0.1.  loss_out (device, 1 float) = mean of
  * the weighted focal MSE; grad_pred (device [B][K][H][W] or NULL) = d loss /
  * d pred; threshold_out (device, 1 float, or NULL) = the threshold used.
- * Deterministic (fixed-order double reductions). */
+ * Deterministic (fixed-order double reductions).  A NaN in gt is outside the
+ * contract: torch.quantile returns NaN for it, the radix select orders it as
+ * a number beyond the infinities and returns a finite threshold. */
 int kpd_adaptive_heatmap_loss(const float* pred, const float* gt, const float* target_weight, int B, int K, int H,
                               int W, float keypoint_weight, float background_weight, int adaptive_threshold,
                               float focal_alpha, float* loss_out, float* grad_pred, float* threshold_out,
