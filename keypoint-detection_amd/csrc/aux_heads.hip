@@ -546,13 +546,7 @@ hipError_t launch_kh_att2(const float* x, const void* w1s, int w1_exp, const flo
                           hipStream_t st) {
   if (R <= 0) return hipSuccess;
   if (!w1s || !bound || bdiv < 1 || bstride < 1 || !hsc || !out) return hipErrorInvalidValue;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = kpd_num_cus();
   const long tiles = (long)R * 49;
   const unsigned grid = (unsigned)std::min<long>(tiles, 4L * ncu);
   hipLaunchKernelGGL(kh_att2_kernel, dim3(grid), dim3(256), 0, st, x, static_cast<const _Float16*>(w1s), w1_exp, b1,

@@ -890,13 +890,7 @@ static hipError_t k6_wgrad(const float* x, const float* gy, int N, int C, int H,
   const int tiles = (Cp / TN) * (Op / TM) * 9;
   // images per K slice: the fewest-rounds x longest-slice product over the
   // resident slots (split: 72 KB of LDS, 2 workgroups per CU; fp32: 4)
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = kpd_num_cus();
   const long slots = (long)ncu * (fp32 ? 4 : TM * TN > kWgT * kWgT ? 1 : 2);   // resident per CU (LDS)
   int ips = N;
   long best = -1;
@@ -962,13 +956,7 @@ static hipError_t k6_wgrad_bf(const float* x, const float* gy, int N, int C, int
   const int TM = O > kWgT ? 256 : kWgT, TN = C > kWgT ? 256 : kWgT;
   const int Cp = (C + TN - 1) / TN * TN, Op = (O + TM - 1) / TM * TM;
   const int tiles = (Cp / TN) * (Op / TM) * 9;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = kpd_num_cus();
   const long slots = (long)ncu * (TM * TN > kWgT * kWgT ? 1 : 2);   // as the split kernel's: the same slices
   int ips = N;
   long best = -1;

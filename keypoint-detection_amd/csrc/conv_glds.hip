@@ -1141,7 +1141,7 @@ constexpr int hm_epi_parts() { return BMH > 256 ? 2 : 1; }
 // DBG (A/B ablations, KPD_HMCONV_DBG): 1 = no MFMA, 2 = no weight / window
 // DMA inside the K loop (the prologue's still lands)
 // BMH: GEMM rows per tile (256, or 224 so that the tile count packs the CUs'
-// rounds better -- launch_hmconv picks it; the window stays 384 rows)
+// rounds better -- hm_schedule picks it; the window stays 384 rows)
 // CIN: input channels as a compile-time constant (0 = p.cin): the K loop's
 // trip count is then known to the compiler, and conv 1 / conv 2 are separate
 // kernels in a trace
@@ -1151,8 +1151,8 @@ constexpr int hm_epi_parts() { return BMH > 256 ? 2 : 1; }
 // DB (SPLIT only): double-buffered fragment sets -- step k+1's operands are
 // all read while step k's three passes run (conv 3: few MFMAs per pass and
 // registers to spare; the BN = 256 tiles have no room for a second set).
-// NW: waves per workgroup (8; 4 for conv 3: 64 x 64 wave tiles, 1.5x fewer
-// LDS fragment bytes per MFMA than 8 waves of 32 x 64, one wave per SIMD).
+// NW: waves per workgroup, always 8 (the parameter keeps its position in the
+// kernels' names, which tools/prof_stages.py and the committed profiles read).
 // MODE: epilogue -- 0 bias + ReLU, re-split (or bf16) for the next conv; 1 the
 // fused final 1x1 + sigmoid (heatmap); 2 KEYPOINT_HEAD (keypoint_head.py:
 // 64-90): bias + ReLU6, the ResidualBlock's bn1 affine + ReLU6, the
@@ -1185,21 +1185,8 @@ constexpr int hmconv_lds_bytes() {
 // position HP + m_off + (L / (cout / BN)) * BMH; lds: the workgroup's LDS
 // (hmconv_lds_bytes), declared by the calling kernel so that kernels running
 // tiles of two heights (hmconv_mixed_kernel) share one allocation.
-// PST (persistent kernel, hmconv_persist_kernel): LDS as [A0 | B0 | A1 | B1]
-// (window buffer c & 1 beside weight stage c & 1), so that after the K loop
-// A0 + B0 take the NEXT tile's prologue (chunk 0 window, B(0): issued before
-// this tile's epilogue when next_m0 >= 0) while the epilogue stages through
-// A1 + B1 in four 112-row x 128-column parts; the epilogue's VMEM operations
-// are a fixed count per wave (buffer stores with out-of-range offsets for
-// border rows, both amax atomics always), so the next tile's first barrier
-// waits for its prologue with a counted vmcnt, not for these stores.
-// pre: this tile's prologue was issued by the previous tile.
-template <int BMH>
-constexpr int hm_pst_stores() { return 2 * 2 * ((BMH / 2 + 31) / 32) * 2; }   // parts x IT x (hi, lo)
-template <int BN, int SB, int DBG, int BMH, bool SPLIT, int CIN, int TPS, bool DB, int NW, int MODE, int NTAP,
-          bool PST = false>
-__device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, const int L, const int m_off,
-                                            const bool pre = false, const int next_m0 = -1) {
+template <int BN, int SB, int DBG, int BMH, bool SPLIT, int CIN, int TPS, bool DB, int NW, int MODE, int NTAP>
+__device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, const int L, const int m_off) {
   constexpr int NTH = NW * 64;
   constexpr int EMODE = MODE >= 0 ? MODE : (BN == 64 ? 1 : 0);
   static_assert(NTAP == 9 || (NTAP == 10 && EMODE == 2 && SPLIT && !DB), "tenth tap: KH downsample");
@@ -1209,8 +1196,8 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
   constexpr int WM = BMH / WAVES_M, FM = WM / 16, FN = 4;
   constexpr int AW = hm_awin<BMH>();
   static_assert(WM % 16 == 0 && BMH + 128 <= AW && AW % (8 * NW) == 0, "tile rows");
-  static_assert(NW == 8 || (BN == 64 && SPLIT && DB), "4 waves: the conv 3 split DB variant only");
-  constexpr int A_LD = AW / 8 / NW;                      // A-window DMA wave-instructions per wave (6; 8 at 384 rows; NW 4: 12)
+  static_assert(NW == 8, "8 waves: the 4-wave conv 3 variant measured slower and was removed; NW only keeps the names");
+  constexpr int A_LD = AW / 8 / NW;                      // A-window DMA wave-instructions per wave (6; 8 at 384 rows)
   static_assert(A_LD <= 9 || TPS > 1, "window pieces: one per tap");
   constexpr int B_LD = BN / 8 / NW;                      // B DMA wave-instructions per wave per K-step
   constexpr int ABUF = AW * ROWB, BSTAGE = BN * ROWB * TPS;
@@ -1218,18 +1205,11 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
   constexpr bool FINAL = EMODE == 1;
   constexpr int NAB = hm_nab<CIN, SPLIT>();
   static_assert(hmconv_lds_bytes<BN, SB, BMH, SPLIT, TPS, NW, MODE, NAB>() <= 160 * 1024, "LDS budget");
-  static_assert(!PST || NAB == 2, "persistent tiles: two window buffers");
-  static_assert(!PST || (SPLIT && EMODE == 0 && SB == 2 && TPS == 1 && !DB && NW == 8 && NTAP == 9 && BN == 256 &&
-                         BMH <= 224 && DBG == 0), "persistent tiles: split conv 1 / conv 2 (BN = cout = 256)");
-  // window buffer of chunk c, weight stage s (PST: [A0 | B0 | A1 | B1])
-  auto a_at = [&](int c) { return PST ? (c & 1) * (ABUF + BSTAGE) : NAB == 1 ? 0 : (c & 1) * ABUF; };
-  auto b_at = [&](int st) { return PST ? st * (ABUF + BSTAGE) + ABUF : NAB * ABUF + st * BSTAGE; };
+  // window buffer of chunk c, weight stage s
+  auto a_at = [&](int c) { return NAB == 1 ? 0 : (c & 1) * ABUF; };
+  auto b_at = [&](int st) { return NAB * ABUF + st * BSTAGE; };
 
-  int tid = threadIdx.x;
-  // PST: per tile, tid is opaque, so that the lane-dependent offsets are
-  // recomputed in every tile instead of hoisted out of the persistent loop
-  // and held (with the tile's own working set they overflow the registers)
-  if constexpr (PST) asm volatile("" : "+v"(tid));
+  const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   // KH mode: column groups by wave halves (waves w and w + 4 share a SIMD, so
   // a group with fewer live columns pairs with a full one on every SIMD)
@@ -1360,22 +1340,12 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
   const int rbound = (rlo + 1) * HPP;       // first padded position of the tile's second ROI
   // prologue: chunk 0's window and the first SB-1 K-steps' weights
   const int KS = KT / TPS;                  // K-steps (barriers)
-  if (!PST || !pre) {
 #pragma unroll
-    for (int i = 0; i < A_LD; ++i) issue_a(0, i);
+  for (int i = 0; i < A_LD; ++i) issue_a(0, i);
 #pragma unroll
-    for (int k = 0; k < SB - 1; ++k)
-      if (k < KS) issue_b(k);
-    barrier_k(KS < SB - 1);
-  } else {
-    // prologue issued by the previous tile, before its epilogue's fixed count
-    // of VMEM operations (hm_pst_stores<224> stores + 2 amax atomics)
-    if (p.amax_idx >= 0) wait_vmcnt<hm_pst_stores<224>() + 2>();
-    else wait_vmcnt<hm_pst_stores<224>()>();
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
+  for (int k = 0; k < SB - 1; ++k)
+    if (k < KS) issue_b(k);
+  barrier_k(KS < SB - 1);
   stamp16(p.stamps, 1);
   stamp16(p.stamps, 6, __builtin_amdgcn_s_memtime());   // shader clock (K-loop clock rate)
   // the next chunk's window, spread over this chunk's K-steps: pieces of
@@ -1587,7 +1557,7 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
       using I0 = std::integral_constant<int, 0>;
       using I1 = std::integral_constant<int, 1>;
       using I2 = std::integral_constant<int, 2>;
-      // the column plans in use (launch_hmconv_kh): [64 + ds | 32 + 32 zero] at
+      // the column plans in use (the KH_* variants): [64 + ds | 32 + 32 zero] at
       // BN 128, [32 + ds | 32 zero] and [16 | 48 zero] at BN 64
       if (BN == 128 && nact == 2 && nact9 == 0) {
         if constexpr (BN == 128) run_loop(I2{}, I2{}, I0{});
@@ -1606,40 +1576,6 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
   stamp16(p.stamps, 7, __builtin_amdgcn_s_memtime());
   __syncthreads();
   stamp16(p.stamps, 2);
-  float pbias[PST ? 2 : 1][8];
-  if constexpr (PST) {
-    // the loads of this tile are consumed here (no compiler wait lands behind
-    // the prefetch below)
-    // the epilogue's bias (this thread's 8 channels of each 128-column half)
-    // is read before the prefetch too (L2 hits, ~0.4 us)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int co = n0 + h * 128 + (tid % 16) * 8;
-      const float4 b0 = *reinterpret_cast<const float4*>(p.bias + co);
-      const float4 b1 = *reinterpret_cast<const float4*>(p.bias + co + 4);
-      pbias[h][0] = b0.x; pbias[h][1] = b0.y; pbias[h][2] = b0.z; pbias[h][3] = b0.w;
-      pbias[h][4] = b1.x; pbias[h][5] = b1.y; pbias[h][6] = b1.z; pbias[h][7] = b1.w;
-    }
-    asm volatile("" ::"v"(us[0]), "v"(us[1]), "v"(os[0]), "v"(os[1]));
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) asm volatile("" ::"v"(pbias[h][e]));
-    // the next tile's prologue into A0 / B0 (free: the last K-step used A1 / B1)
-    if (next_m0 >= 0) {
-      const int nwb = max(next_m0 - 64, 0);
-      const i32x4 nrin = make_rsrc(static_cast<const char*>(p.in) + (size_t)nwb * RB,
-                                   (int)min(((long)Mtot - nwb) * RB, 0x7fffffffL));
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) {
-        const int m = next_m0 - 64 + wave * (AW / NW) + i * 8 + lrow;
-        const unsigned off = (m >= 0 && m < Mtot) ? (unsigned)((m - nwb) * RB + lchunk * 16) : OOB;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + a_at(0) + (wave * (AW / NW) + i * 8) * ROWB);
-        glds16(nrin, dst, off, 0);
-      }
-      issue_b(0);
-    }
-  }
 
   // interior test of a padded position: ROI row/column 1..56
   auto interior = [&](int m, int& r, int& yy, int& xx) {
@@ -1649,64 +1585,7 @@ __device__ __forceinline__ void hmconv_tile(const HmConvArgs& p, char* lds, cons
     xx = rem - (yy + 1) * HP;
     return m < Mtot && yy >= 0 && xx < HMS;
   };
-  if constexpr (PST) {
-    // four parts of 112 rows x 128 columns staged through A1 + B1; every
-    // wave issues exactly hm_pst_stores<BMH>() stores (border / out-of-tile
-    // rows to an out-of-range offset) and, with amax, two atomics
-    float* tile = reinterpret_cast<float*>(lds + ABUF + BSTAGE);
-    constexpr int P4 = 128 + 4, C8 = 16, RS = NTH / C8, IT = (WM + RS - 1) / RS;
-    static_assert(WAVES_M == 2 && WM * P4 * 4 <= ABUF + BSTAGE && 4 * IT * 2 == hm_pst_stores<BMH>(), "PST epilogue");
-    const int obytes = p.cout * 4;
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(p.out) + (size_t)m0 * obytes,
-                                                                          (short)0, BMH * obytes, 0x00020000);
-    float mx[2] = {0.f, 0.f};
-    const int c8 = tid % C8, row0 = tid / C8;
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const int pr = pp >> 1, h = pp & 1;
-      if (pp) __syncthreads();
-      if (wn / 2 == h && wm == pr) acc_to_lds<FM, FN, WM, 64, 128>(tile, acc, 0, wn % 2, lane);
-      __syncthreads();
-      const int co = n0 + h * 128 + c8 * 8;
-#pragma unroll
-      for (int it = 0; it < IT; ++it) {
-        const int row = row0 + it * RS, m = m0 + pr * WM + row;
-        int r, yy, xx;
-        const bool ok = row < WM && interior(m, r, yy, xx);
-        const float4 x0 = *reinterpret_cast<const float4*>(tile + min(row, WM - 1) * P4 + c8 * 8);
-        const float4 x1 = *reinterpret_cast<const float4*>(tile + min(row, WM - 1) * P4 + c8 * 8 + 4);
-        const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        const int q = m >= rbound;
-        const float u = q ? us[1] : us[0], sc = q ? os[1] : os[0];
-        f16x8 hi, lo;
-        float mc = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float v = fmaxf(fmaf(xv[e], u, pbias[h][e]), 0.f);
-          mc = fmaxf(mc, v);
-          const float xs = v * sc;
-          hi[e] = (_Float16)xs;
-          lo[e] = (_Float16)(xs - (float)hi[e]);
-        }
-        const unsigned off = ok ? (unsigned)((m - m0) * obytes + (co >> 5) * 128 + (co & 31) * 2) : OOB;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), rout, off, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), rout, ok ? off + 64 : OOB, 0, 0);
-        if (ok) {
-          if (q) mx[1] = fmaxf(mx[1], mc); else mx[0] = fmaxf(mx[0], mc);
-        }
-      }
-    }
-    if (p.amax_idx >= 0) {   // per-ROI max|out| for the next conv's output scale: two atomics per wave, always
-      const float w0 = wave_max(mx[0]), w1 = wave_max(mx[1]);
-      if (lane == 0) {
-        const bool two = rlo + 1 < p.R;
-        unsigned* a0 = reinterpret_cast<unsigned*>(p.hsc + (size_t)(p.r0 + rlo) * 4 + p.amax_idx);
-        unsigned* a1 = reinterpret_cast<unsigned*>(p.hsc + (size_t)(p.r0 + rlo + (two ? 1 : 0)) * 4 + p.amax_idx);
-        atomicMax(a0, __float_as_uint(w0));
-        atomicMax(a1, __float_as_uint(two ? w1 : 0.f));
-      }
-    }
-  } else if constexpr (EMODE == 0 || EMODE == 3) {
+  if constexpr (EMODE == 0 || EMODE == 3) {
     // bias + ReLU through the LDS tile (two 128-column halves): bf16 16-byte
     // row stores, or (SPLIT) the unscaled fp32 value re-split for the next
     // conv: x * 2^a_out(ROI) as f16 hi / lo into the [hi32 | lo32] groups
@@ -2044,51 +1923,6 @@ __global__ __launch_bounds__(NW * 64) void hmconv_kernel(const HmConvArgs p) {
                                                                         p.m_off);
 }
 
-// Persistent heatmap conv 1 / conv 2 (split, BN = cout = 256): one
-// workgroup per CU walks full 224-row tiles t = w, w + G, ... (w: the
-// XCD-contiguous rank of the workgroup, as xcd_remap) and then tail tile w of
-// 192 rows if w < mix_H; each tile issues the next one's prologue (chunk 0
-// window + B(0)) before its epilogue (hmconv_tile PST).  mix_F full tiles
-// (whole rounds), mix_H tail tiles (exact count, <= G).
-// the kernel's argument block re-read from the kernarg segment (scalar loads;
-// the asm hides the pointer's provenance so that nothing is kept live across
-// a persistent loop's iterations)
-template <typename T>
-__device__ __forceinline__ void kernarg_copy(T& dst) {
-  typedef const __attribute__((address_space(4))) unsigned* KaPtr;
-  KaPtr ka = (KaPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(ka));
-  static_assert(sizeof(T) % 4 == 0, "argument block");
-  unsigned* d = reinterpret_cast<unsigned*>(&dst);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) d[i] = ka[i];
-}
-
-template <int CIN>
-__global__ __launch_bounds__(512) void hmconv_persist_kernel(const HmConvArgs p) {
-  __shared__ __attribute__((aligned(1024))) char lds[hmconv_lds_bytes<256, 2, 224, true, 1, 8, -1>()];
-  const int G = gridDim.x, w = xcd_remap(blockIdx.x, G);
-  const int F = p.mix_F, H = p.mix_H, tail_off = p.m_off + F * 224;
-  bool pre = false;
-  for (int t = w; t < F; t += G) {
-    // the arguments are re-read from the kernarg segment every tile (scalar
-    // loads) instead of held in SGPRs across the loop: the held copy pushed
-    // the tile body past the register budget (spills)
-    HmConvArgs pl;
-    kernarg_copy(pl);
-    const int nt = t + G;
-    const int next_m0 = nt < F ? HP + pl.m_off + nt * 224 : (w < H ? HP + tail_off + w * 192 : -1);
-    hmconv_tile<256, 2, 0, 224, true, CIN, 1, false, 8, -1, 9, true>(pl, lds, t, pl.m_off, pre, next_m0);
-    pre = next_m0 >= 0;
-  }
-  if (w < H) {
-    HmConvArgs pl;
-    kernarg_copy(pl);
-    hmconv_tile<256, 2, 0, 192, true, CIN, 1, false, 8, -1, 9, true>(pl, lds, w, tail_off, pre, -1);
-  }
-  wait_vmcnt<0>();
-}
-
 // Full rounds of BMH-row tiles and a last round of BMT-row tiles (the rows
 // left over), in ONE launch whose first round mixes the two: on every XCD
 // half of the first round's workgroups take a short tail tile, so those CUs
@@ -2175,350 +2009,256 @@ hipError_t launch_conv16(const Conv16Args& a, int split, int out_bf16, hipStream
   return hipErrorInvalidValue;
 }
 
-// KEYPOINT_HEAD convs (MODE 2): cin 128 / 64 / 32 (compile-time), cout 128 or
-// 64 (one column tile), the downsample as a tenth tap or not
-static hipError_t launch_hmconv_kh(const HmConvArgs& a0, hipStream_t st) {
-  if (!a0.split || !a0.hsc || a0.in_idx < 0 || a0.in_idx > 3 || (a0.ns > 0 && (!a0.out || a0.out_idx < 0 ||
-      a0.out_idx > 3 || a0.ns % 32)) || (a0.nf > 0 && !a0.outf) || a0.nf % 16 || a0.ns + a0.nf > a0.cout ||
-      (a0.ntap != 9 && a0.ntap != 10) || (a0.ntap == 10 && !a0.kh_bd) || !a0.kh_pt || !a0.bias)
-    return hipErrorInvalidValue;
-  const int sel = (a0.cin == 128 && a0.cout == 128 && a0.ntap == 10) ? 1
-                : (a0.cin == 64 && a0.cout == 64 && a0.ntap == 10) ? 2
-                : (a0.cin == 32 && a0.cout == 64 && a0.ntap == 9) ? 3 : 0;
-  if (!sel) return hipErrorInvalidValue;
-  // the staged BN = 128 epilogue adds the downsample (tenth-tap) accumulator
-  // to columns 0..63 only: a wider identity branch is not expressible there
-  if (sel == 1 && a0.ns > 64) return hipErrorInvalidValue;
-  HmConvArgs a = a0;
-  const long wt_bytes = (long)a.cout * a.ntap * a.cin * 4, roi_bytes = (long)HPP * a.cin * 4;
-  if (wt_bytes > kMaxDesc) return hipErrorInvalidValue;
-  a.wt_bytes = (int)wt_bytes;
-  a.m_off = 0;
-  // staggered DMA issue (waves 4-7 one pass later, as the heatmap convs):
-  // KEYPOINT_HEAD stage at C3 4.41 / 4.51 vs 4.53 / 4.58 ms (same-box A/B,
-  // KPD_KH_NOSTAGGER=1: off)
-  static const bool kh_nostagger = kpd_diag_env("KPD_KH_NOSTAGGER") != nullptr;
-  a.stagger = kh_nostagger ? 0 : 1;
-  // one launch for all ROIs (the kernel's input descriptor is per tile); the
-  // GEMM row index stays a 32-bit int
-  if ((long)a0.R * HPP >= 0x7fffffffL) return hipErrorInvalidValue;
-  const int chunk = a0.R;
-  for (int r0 = 0; r0 < a0.R; r0 += chunk) {
-    const int nr = std::min(chunk, a0.R - r0);
-    a.R = nr;
-    a.r0 = a0.r0 + r0;
-    a.in = static_cast<const char*>(a0.in) + (size_t)r0 * roi_bytes;
-    if (a0.out) a.out = static_cast<char*>(a0.out) + (size_t)r0 * HPP * a.ns * 4;
-    if (a0.outf) a.outf = a0.outf + (size_t)r0 * HMS * HMS * a.nf;
-    a.in_bytes = (int)std::min<long>((long)nr * roi_bytes, kMaxDesc);   // (unused: per-tile descriptors)
-    const long rows = (long)nr * HPP - HP;
-    const dim3 grid((unsigned)((rows + BM - 1) / BM));
-    // the regression conv (cin 32: one input chunk, one window per tile)
-    // takes 512-row tiles: 64 x 64 per wave (0.83 fragment reads per MFMA
-    // instead of 1.0) and half the per-tile prologues / epilogues of its
-    // 3 K-steps
-    const dim3 grid512((unsigned)((rows + 511) / 512));
-    // ResidualBlock 2 (cin 64, 32 live columns): 384-row tiles, 48 x 64 per
-    // wave (a 512-row window pair + two weight stages fill the 160 KB)
-    const dim3 grid384((unsigned)((rows + 383) / 384));
-    static const bool kh_bm256 = kpd_diag_env("KPD_KH_BM256") != nullptr;   // A/B: 256-row tiles for both
-    // two taps per K-step (three for the 32-channel conv): one barrier per
-    // 2-3 taps of MFMAs -- these convs have 96 / 32 / 16 live output columns,
-    // so a single tap's MFMAs are too few to amortise a barrier and the DMA
-    // issue (MFMA busy 0.37 at one tap per step).  KPD_KH_TPS1=1: one tap (A/B).
-    static const bool tps1 = kpd_diag_env("KPD_KH_TPS1") != nullptr;
-    if (tps1) {
-      if (sel == 1) hipLaunchKernelGGL((hmconv_kernel<128, 3, 0, BM, true, 128, 1, false, 8, 2, 10>), grid, dim3(NT), 0, st, a);
-      else if (sel == 2) hipLaunchKernelGGL((hmconv_kernel<64, 4, 0, BM, true, 64, 1, false, 8, 2, 10>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((hmconv_kernel<64, 4, 0, BM, true, 32, 1, false, 8, 2, 9>), grid, dim3(NT), 0, st, a);
-    } else if (kh_bm256) {
-      if (sel == 1) hipLaunchKernelGGL((hmconv_kernel<128, 2, 0, BM, true, 128, 2, false, 8, 2, 10>), grid, dim3(NT), 0, st, a);
-      else if (sel == 2) hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, BM, true, 64, 2, false, 8, 2, 10>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, BM, true, 32, 3, false, 8, 2, 9>), grid, dim3(NT), 0, st, a);
-    } else {
-      if (sel == 1) hipLaunchKernelGGL((hmconv_kernel<128, 2, 0, BM, true, 128, 2, false, 8, 2, 10>), grid, dim3(NT), 0, st, a);
-      else if (sel == 2) hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, 384, true, 64, 2, false, 8, 2, 10>), grid384, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, 512, true, 32, 3, false, 8, 2, 9>), grid512, dim3(NT), 0, st, a);
+// ---- hmconv host side: the variant table, the schedule, the launcher ----
+//
+// Every hmconv_kernel<BN, SB, DBG, BMH, SPLIT, CIN, TPS, DB, NW, MODE, NTAP> and
+// hmconv_mixed_kernel<BN, SB, BMH, BMT, CIN, TPS, DB, MODE> instantiation,
+// written once.  (Alternatives that lost their measurement are not kept as
+// variants: DESIGN.md records them with the last commit that had them.)
+#define HM_VARIANTS(X)                                                                        \
+  /* heatmap conv 1 / 2, split: 256 columns, 2-stage weight ring; 224-row tiles with cin    \
+     64 / 256 / runtime, conv 2's 160- and 192-row tail tiles, conv 1's mixed first round */  \
+  X(S224_C64, (hmconv_kernel<256, 2, 0, 224, true, 64>))                                      \
+  X(S224_C256, (hmconv_kernel<256, 2, 0, 224, true, 256>))                                    \
+  X(S160_C256, (hmconv_kernel<256, 2, 0, 160, true, 256>))                                    \
+  X(S192_C256, (hmconv_kernel<256, 2, 0, 192, true, 256>))                                    \
+  X(MIX160_C64, (hmconv_mixed_kernel<256, 2, 224, 160, 64, 1, false, -1>))                    \
+  X(MIX192_C64, (hmconv_mixed_kernel<256, 2, 224, 192, 64, 1, false, -1>))                    \
+  X(S224, (hmconv_kernel<256, 2, 0, 224, true>))                                              \
+  X(S256, (hmconv_kernel<256, 2, 0, BM, true>))                                               \
+  X(S256_N128, (hmconv_kernel<128, 4, 0, BM, true>))                                          \
+  /* conv 3 + fused final layer, split: three taps per K-step, two fragment sets (cin 256) */ \
+  X(S3_256, (hmconv_kernel<64, 2, 0, BM, true, 256, 3, true>))                                \
+  X(S3_128, (hmconv_kernel<64, 2, 0, 128, true, 256, 3, true>))                               \
+  X(S3_ANY, (hmconv_kernel<64, 4, 0, BM, true>))                                              \
+  /* the same convs on bf16 operands (precision "mixed") */                                   \
+  X(B224_C64, (hmconv_kernel<256, 2, 0, 224, false, 64>))                                     \
+  X(B224_C256, (hmconv_kernel<256, 2, 0, 224, false, 256>))                                   \
+  X(B224, (hmconv_kernel<256, 2, 0, 224>))                                                    \
+  X(B256, (hmconv_kernel<256, 2>))                                                            \
+  X(B256_N128, (hmconv_kernel<128, 4>))                                                       \
+  X(B3_256, (hmconv_kernel<64, 4>))                                                           \
+  X(B3_128, (hmconv_kernel<64, 4, 0, 128>))                                                   \
+  /* KEYPOINT_HEAD (MODE 2): ResidualBlock 1 / 2 with the downsample as a tenth tap, and    \
+     the regression conv */                                                                   \
+  X(KH_RB1, (hmconv_kernel<128, 2, 0, BM, true, 128, 2, false, 8, 2, 10>))                    \
+  X(KH_RB2, (hmconv_kernel<64, 2, 0, 384, true, 64, 2, false, 8, 2, 10>))                     \
+  X(KH_REG, (hmconv_kernel<64, 2, 0, 512, true, 32, 3, false, 8, 2, 9>))                      \
+  /* linear fp32 output (MODE 3), split and bf16: cout 256 as conv 1 / 2's tiles, cout 128  \
+     as 256 x 128 tiles with a 4-stage ring */                                                \
+  X(LS224_C64, (hmconv_kernel<256, 2, 0, 224, true, 64, 1, false, 8, 3>))                     \
+  X(LS224_C256, (hmconv_kernel<256, 2, 0, 224, true, 256, 1, false, 8, 3>))                   \
+  X(LS256_C64, (hmconv_kernel<128, 4, 0, BM, true, 64, 1, false, 8, 3>))                      \
+  X(LS256_C256, (hmconv_kernel<128, 4, 0, BM, true, 256, 1, false, 8, 3>))                    \
+  X(LB224_C64, (hmconv_kernel<256, 2, 0, 224, false, 64, 1, false, 8, 3>))                    \
+  X(LB224_C256, (hmconv_kernel<256, 2, 0, 224, false, 256, 1, false, 8, 3>))                  \
+  X(LB256_C64, (hmconv_kernel<128, 4, 0, BM, false, 64, 1, false, 8, 3>))                     \
+  X(LB256_C256, (hmconv_kernel<128, 4, 0, BM, false, 256, 1, false, 8, 3>))
+#if KPD_DIAG
+// ablations (KPD_HMCONV_DBG=1: no MFMA, 2: no K-loop DMA); wrong results by design
+#define HM_DIAG_VARIANTS(X)                                          \
+  X(D1_S3, (hmconv_kernel<64, 2, 1, BM, true, 256, 3, true>))        \
+  X(D2_S3, (hmconv_kernel<64, 2, 2, BM, true, 256, 3, true>))        \
+  X(D1_S224, (hmconv_kernel<256, 2, 1, 224, true, 256>))             \
+  X(D2_S224, (hmconv_kernel<256, 2, 2, 224, true, 256>))             \
+  X(D1_B256, (hmconv_kernel<256, 2, 1>))                             \
+  X(D2_B256, (hmconv_kernel<256, 2, 2>))
+#else
+#define HM_DIAG_VARIANTS(X)
+#endif
+
+enum HmVariant {
+#define X(id, kernel) HM_##id,
+  HM_VARIANTS(X) HM_DIAG_VARIANTS(X)
+#undef X
+};
+
+// One launch of a schedule: the variant, its grid (workgroups of NT threads),
+// the first GEMM row of tile 0, and hmconv_mixed_kernel's tile counts.
+struct HmLaunch {
+  HmVariant v;
+  unsigned grid;
+  int m_off, mix_F, mix_H, mix_lead;
+};
+struct HmSchedule {
+  int n;
+  HmLaunch l[2];
+};
+
+static void hm_launch(const HmLaunch& l, HmConvArgs a, hipStream_t st) {
+  a.m_off = l.m_off;
+  a.mix_F = l.mix_F;
+  a.mix_H = l.mix_H;
+  a.mix_lead = l.mix_lead;
+  switch (l.v) {
+#define X(id, kernel) case HM_##id: hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(NT), 0, st, a); break;
+    HM_VARIANTS(X) HM_DIAG_VARIANTS(X)
+#undef X
+  }
+}
+
+// The diagnostic build's A/B switches, read once (the production build reads
+// none: kpd_diag_env is a constant null there, and these are the defaults).
+struct HmKnobs {
+  int bm;           // KPD_HMCONV_BM=224 / 256: conv 1 / 2's tile rows
+  int dbg;          // KPD_HMCONV_DBG: ablations
+  bool stagger;     // KPD_HM_NOSTAGGER=1: off.  Staggered DMA issue of the split K loop
+  bool kh_stagger;  // KPD_KH_NOSTAGGER=1: off.  KEYPOINT_HEAD stage at C3 4.41 / 4.51 vs 4.53 / 4.58 ms (same-box A/B)
+  bool tail3;       // KPD_HM3_NOTAIL=1: off.  Conv 3's tail launch
+  bool tail12;      // KPD_HM12_NOTAIL=1: off.  Conv 2's tail launch
+  bool mix;         // KPD_HM_MIX=0: off.  Conv 1's mixed first round
+};
+static const HmKnobs& hm_knobs() {
+  static const HmKnobs k = {
+      kpd_diag_env("KPD_HMCONV_BM") ? atoi(kpd_diag_env("KPD_HMCONV_BM")) : 0,
+      kpd_diag_env("KPD_HMCONV_DBG") ? atoi(kpd_diag_env("KPD_HMCONV_DBG")) : 0,
+      kpd_diag_env("KPD_HM_NOSTAGGER") == nullptr,
+      kpd_diag_env("KPD_KH_NOSTAGGER") == nullptr,
+      kpd_diag_env("KPD_HM3_NOTAIL") == nullptr,
+      kpd_diag_env("KPD_HM12_NOTAIL") == nullptr,
+      !kpd_diag_env("KPD_HM_MIX") || atoi(kpd_diag_env("KPD_HM_MIX")) != 0,
+  };
+  return k;
+}
+
+// Which kernels a (validated) call gets, on which grids: pure host code, no
+// HIP call.  One launch covers all ROIs (the kernel's input descriptor is per
+// tile, so the 31-bit extent bounds a tile's window only).  Tile heights never
+// change the arithmetic of a row (same K order), so every split of the rows
+// into launches gives the same results.  Tile counts in the comments: 64 ROIs,
+// rows = 64 * 3249 - 57 = 207879, 256 CUs.
+static HmSchedule hm_schedule(const HmConvArgs& a, const int ncu, const HmKnobs& k) {
+  const long rows = (long)a.R * HPP - HP;
+  auto tiles = [&](long bm) { return (rows + bm - 1) / bm; };
+  auto one = [](HmVariant v, long grid) { return HmSchedule{1, {{v, (unsigned)grid, 0, 0, 0, 0}}}; };
+  // F full tiles of bm rows, then H tail tiles from row F * bm on
+  auto two = [](HmVariant full, long F, long bm, HmVariant tail, long H) {
+    return HmSchedule{2, {{full, (unsigned)F, 0, 0, 0, 0}, {tail, (unsigned)H, (int)(F * bm), 0, 0, 0}}};
+  };
+  const bool split = a.split != 0, c64 = a.cin == 64;
+
+  // KEYPOINT_HEAD convs: cin 128 / 64 / 32 (compile-time), one column tile.
+  // Two taps per K-step (three for the 32-channel conv): these convs have
+  // 96 / 32 / 16 live output columns, so a single tap's MFMAs are too few to
+  // amortise a barrier and the DMA issue (MFMA busy 0.37 at one tap per step).
+  // ResidualBlock 2 (cin 64, 32 live columns): 384-row tiles, 48 x 64 per
+  // wave (a 512-row window pair + two weight stages fill the 160 KB).  The
+  // regression conv (cin 32: one input chunk, one window per tile): 512-row
+  // tiles, 64 x 64 per wave (0.83 fragment reads per MFMA instead of 1.0) and
+  // half the per-tile prologues / epilogues of its 3 K-steps.
+  if (a.kh_ps) return a.cin == 128 ? one(HM_KH_RB1, tiles(BM)) : c64 ? one(HM_KH_RB2, tiles(384)) : one(HM_KH_REG, tiles(512));
+
+  // Linear mode: cin 64 or 256; cout 256, or 128 (a 64-channel output padded with zero weights)
+  if (a.outf && !a.out && !a.fin_w) {
+    if (a.cout == 256) return one(split ? (c64 ? HM_LS224_C64 : HM_LS224_C256) : (c64 ? HM_LB224_C64 : HM_LB224_C256), tiles(224));
+    return one(split ? (c64 ? HM_LS256_C64 : HM_LS256_C256) : (c64 ? HM_LB256_C64 : HM_LB256_C256), tiles(BM));
+  }
+
+  // The heatmap convs.  BN 256 with a 2-stage weight ring measured faster than
+  // BN 128 with 4 stages for conv 1 / 2 (89 / 233 us vs 92 / 256 us at 64
+  // ROIs): the wider tile halves the weight bytes per MFMA; conv 3 has 64 outputs
+  const bool fin = a.fin_w != nullptr;
+  const int bn = fin ? 64 : (a.cout % 256 == 0 ? 256 : 128);
+  // BN 256: 224-row tiles when that packs the rounds of one workgroup per CU
+  // better (929 tiles = 4 rounds of 224 rows instead of 813 = 4 rounds of
+  // 256, the last one 18 % full).  Conv 1 / 2 (cin 64 / 256) always take them:
+  // those are the instances with the input channels as a compile-time
+  // constant (the generic runtime-cin kernel ran conv 1 + 2 at 640 ROIs (C3)
+  // ~2x slower), and conv 2's tail launch packs the last round
+  auto cost = [&](long bm) { return (tiles(bm) * (a.cout / bn) + ncu - 1) / ncu * bm; };
+  const bool spec = c64 || a.cin == 256;
+  const int bm = fin || bn != 256 ? BM : k.bm == 224 || k.bm == BM ? k.bm : (spec || cost(224) < cost(BM)) ? 224 : BM;
+  const long grid = tiles(bm) * (a.cout / bn);
+  const bool plain = !k.dbg && !a.stamps;   // (ablations and phase stamps take single launches)
+
+  // Conv 3 (BN 64, one tile per CU round): a partial last round of 256-row
+  // tiles (813 tiles = 3.2 rounds, the 4th 18 % full) goes out as 128-row
+  // tiles in one extra launch instead (768 + 89: a half-length round).
+  if (fin && plain && k.tail3 && (!split || a.cin == 256)) {
+    const long F = rows / BM / ncu * ncu, H = (rows - F * BM + 127) / 128;
+    if (F > 0 && H > 0 && H <= ncu) return split ? two(HM_S3_256, F, BM, HM_S3_128, H) : two(HM_B3_256, F, BM, HM_B3_128, H);
+  }
+  // Conv 1 / 2 (split, 224-row tiles): complete rounds of 224-row tiles, then
+  // the remaining rows as tail tiles: 160 rows when those fit one round, else
+  // 192 (768 + 225 x 160 instead of 929 x 224)
+  if (split && !fin && bn == 256 && bm == 224 && spec && plain) {
+    const long F = rows / 224 / ncu * ncu, rem = rows - F * 224;
+    const bool t160 = (rem + 159) / 160 <= ncu;
+    const long H = t160 ? (rem + 159) / 160 : (rem + 191) / 192;
+    // Conv 1: one launch whose first round mixes both tile heights
+    // (hmconv_mixed_kernel).  Same-box A/B (round 4, 64 ROIs): conv 1 178 /
+    // 180 vs 183 / 182 us (it has no tail launch of its own, so it also
+    // gains the tail tiles' packing), conv 2 502 / 504 vs 500 / 500 -- on
+    // for conv 1 only
+    if (k.mix && c64 && ncu % 8 == 0 && F >= ncu && H > 0 && H <= ncu) {
+      const long H8 = (H + 7) / 8 * 8;   // a share per XCD; tiles past the rows return at once
+      // (mix_lead: half of each XCD's CUs start with a tail tile)
+      return HmSchedule{1, {{t160 ? HM_MIX160_C64 : HM_MIX192_C64, (unsigned)(F + H8), 0, (int)F, (int)H8, ncu / 16}}};
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    // Conv 2: the tail tiles as a second launch (the last round 0.71 as
+    // long with 160-row tiles): 0.528 -> 0.515 ms with 192-row tails.  Conv 1
+    // (18 K-steps a tile, so the per-tile prologue / epilogue dominate)
+    // measured 2 % slower with it.
+    if (!c64 && k.tail12 && F > 0 && rem > 0 && H <= ncu) return two(HM_S224_C256, F, 224, t160 ? HM_S160_C256 : HM_S192_C256, H);
   }
-  return hipSuccess;
+  // a single launch of bm-row tiles
+#if KPD_DIAG
+  if (split && k.dbg) return one(fin ? (k.dbg == 1 ? HM_D1_S3 : HM_D2_S3) : (k.dbg == 1 ? HM_D1_S224 : HM_D2_S224), grid);
+  if (!split && !fin && bn == 256 && (k.dbg == 1 || k.dbg == 2)) return one(k.dbg == 1 ? HM_D1_B256 : HM_D2_B256, grid);
+#endif
+  if (fin) return one(!split ? HM_B3_256 : a.cin == 256 ? HM_S3_256 : HM_S3_ANY, grid);
+  if (bn != 256) return one(split ? HM_S256_N128 : HM_B256_N128, grid);
+  if (bm != 224 || (!split && k.dbg)) return one(split ? HM_S256 : HM_B256, grid);
+  if (split) return one(c64 ? HM_S224_C64 : a.cin == 256 ? HM_S224_C256 : HM_S224, grid);
+  return one(c64 ? HM_B224_C64 : a.cin == 256 ? HM_B224_C256 : HM_B224, grid);
 }
 
-// Linear mode (outf set, out / fin / kh_ps null; split): fp32 NHWC output of
-// acc * u + bias, no activation -- the conv3x3 forward and dgrad of K6
-// (conv3_grad.hip) on the heatmap convs' 56 x 56 maps; cin 64 or 256, cout 256
-// (or 128: a 64-channel output padded with zero weights).
-static hipError_t launch_hmconv_linear(const HmConvArgs& a0, hipStream_t st) {
-  if (!a0.split || !a0.hsc || a0.in_idx < 0 || a0.in_idx > 3 || !a0.bias || (a0.cout != 256 && a0.cout != 128) ||
-      (a0.cin != 64 && a0.cin != 256) || (long)a0.R * HPP >= 0x7fffffffL)
-    return hipErrorInvalidValue;
-  HmConvArgs a = a0;
-  const long wt_bytes = (long)a.cout * 9 * a.cin * 4;
-  if (wt_bytes > kMaxDesc) return hipErrorInvalidValue;
-  a.wt_bytes = (int)wt_bytes;
-  a.m_off = 0;
-  a.r0 = 0;
-  a.stagger = 1;
-  a.out_idx = -1;
-  a.amax_idx = -1;
-  a.in_bytes = (int)std::min<long>((long)a.R * HPP * a.cin * 4, kMaxDesc);
-  const long rows = (long)a.R * HPP - HP;
-  // cout 256: the heatmap conv 1 / 2 tiles (224 x 256, 2-stage weight ring);
-  // cout 128: 256 x 128 tiles with a 4-stage ring (the split BN = 128 variant)
-  if (a.cout == 256) {
-    const dim3 grid((unsigned)((rows + 223) / 224));
-    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, true, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, true, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-  } else {
-    const dim3 grid((unsigned)((rows + BM - 1) / BM));
-    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, true, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, true, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-  }
-  return hipGetLastError();
-}
-
-// Linear mode on bf16 operands (split == 0: conv3x3's precision "mixed",
-// DESIGN.md §3i): the non-split K loop (one v_mfma_f32_16x16x32_bf16 per
-// fragment pair), fp32 NHWC output of acc + bias; the shapes and tiles of
-// launch_hmconv_linear, no scales
-static hipError_t launch_hmconv_linear_bf16(const HmConvArgs& a0, hipStream_t st) {
-  if (!a0.bias || (a0.cout != 256 && a0.cout != 128) || (a0.cin != 64 && a0.cin != 256) ||
-      (long)a0.R * HPP >= 0x7fffffffL)
-    return hipErrorInvalidValue;
-  HmConvArgs a = a0;
-  const long wt_bytes = (long)a.cout * 9 * a.cin * 2;
-  if (wt_bytes > kMaxDesc) return hipErrorInvalidValue;
-  a.wt_bytes = (int)wt_bytes;
-  a.m_off = 0;
-  a.r0 = 0;
-  a.stagger = 0;
-  a.out_idx = -1;
-  a.amax_idx = -1;
-  a.in_bytes = (int)std::min<long>((long)a.R * HPP * a.cin * 2, kMaxDesc);
-  const long rows = (long)a.R * HPP - HP;
-  if (a.cout == 256) {
-    const dim3 grid((unsigned)((rows + 223) / 224));
-    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, false, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, false, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-  } else {
-    const dim3 grid((unsigned)((rows + BM - 1) / BM));
-    if (a.cin == 64) hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, false, 64, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((hmconv_kernel<128, 4, 0, BM, false, 256, 1, false, 8, 3>), grid, dim3(NT), 0, st, a);
-  }
-  return hipGetLastError();
-}
-
+// The three users of the tile, told apart by their arguments: KEYPOINT_HEAD
+// (kh_ps set; split only), linear mode (outf set, out / fin / kh_ps null: fp32
+// NHWC output of acc * u + bias, no activation -- the conv3x3 forward and
+// dgrad of K6, conv3_grad.hip, on the heatmap convs' 56 x 56 maps; split, or
+// bf16 operands without scales for conv3x3's precision "mixed", DESIGN.md
+// §3i), and the heatmap convs.
 hipError_t launch_hmconv(const HmConvArgs& a0, hipStream_t st) {
   if (a0.R <= 0) return hipSuccess;
-  if (a0.kh_ps) return launch_hmconv_kh(a0, st);
-  if (a0.outf && !a0.out && !a0.fin_w) return a0.split ? launch_hmconv_linear(a0, st) : launch_hmconv_linear_bf16(a0, st);
+  const bool kh = a0.kh_ps != nullptr, linear = !kh && a0.outf && !a0.out && !a0.fin_w;
   const bool fin = a0.fin_w != nullptr, split = a0.split != 0;
-  if (a0.cin % (split ? 32 : 64) || (fin ? a0.cout != 64 : a0.cout % 128) ||
-      (fin && (!a0.slot || !a0.heat || !a0.fin_b)) || (!fin && !a0.out) ||
-      (split && (!a0.hsc || a0.in_idx < 0 || a0.in_idx > 3 || a0.amax_idx > 3 || a0.out_idx > 3 ||
-                 (!fin && a0.out_idx < 0))))
+  if (kh) {
+    if (!a0.split || !a0.hsc || a0.in_idx < 0 || a0.in_idx > 3 || (a0.ns > 0 && (!a0.out || a0.out_idx < 0 ||
+        a0.out_idx > 3 || a0.ns % 32)) || (a0.nf > 0 && !a0.outf) || a0.nf % 16 || a0.ns + a0.nf > a0.cout ||
+        (a0.ntap != 9 && a0.ntap != 10) || (a0.ntap == 10 && !a0.kh_bd) || !a0.kh_pt || !a0.bias)
+      return hipErrorInvalidValue;
+    if (!(a0.cin == 128 && a0.cout == 128 && a0.ntap == 10) && !(a0.cin == 64 && a0.cout == 64 && a0.ntap == 10) &&
+        !(a0.cin == 32 && a0.cout == 64 && a0.ntap == 9))
+      return hipErrorInvalidValue;
+    // the staged BN = 128 epilogue adds the downsample (tenth-tap) accumulator
+    // to columns 0..63 only: a wider identity branch is not expressible there
+    if (a0.cin == 128 && a0.ns > 64) return hipErrorInvalidValue;
+  } else if (linear) {
+    if ((split && (!a0.hsc || a0.in_idx < 0 || a0.in_idx > 3)) || !a0.bias || (a0.cout != 256 && a0.cout != 128) ||
+        (a0.cin != 64 && a0.cin != 256))
+      return hipErrorInvalidValue;
+  } else if (a0.cin % (split ? 32 : 64) || (fin ? a0.cout != 64 : a0.cout % 128) ||
+             (fin && (!a0.slot || !a0.heat || !a0.fin_b)) || (!fin && !a0.out) ||
+             (split && (!a0.hsc || a0.in_idx < 0 || a0.in_idx > 3 || a0.amax_idx > 3 || a0.out_idx > 3 ||
+                        (!fin && a0.out_idx < 0)))) {
     return hipErrorInvalidValue;
-  HmConvArgs a = a0;
-  const long es = split ? 4 : 2;   // bytes per channel: bf16, or f16 hi + lo
-  const long wt_bytes = (long)a.cout * 9 * a.cin * es, roi_bytes = (long)HPP * a.cin * es;
-  if (wt_bytes > kMaxDesc) return hipErrorInvalidValue;
-  a.wt_bytes = (int)wt_bytes;
-  // one launch for all ROIs (the kernel's input descriptor is per tile, so
-  // the 31-bit extent bounds a tile's window only); row indices stay 32-bit
-  if ((long)a0.R * HPP >= 0x7fffffffL) return hipErrorInvalidValue;
-  const int chunk = a0.R;
-  for (int r0 = 0; r0 < a0.R; r0 += chunk) {
-    const int nr = std::min(chunk, a0.R - r0);
-    a.R = nr;
-    a.r0 = a0.r0 + r0;
-    a.in = static_cast<const char*>(a0.in) + (size_t)r0 * roi_bytes;
-    if (!fin) a.out = static_cast<char*>(a0.out) + (size_t)r0 * HPP * a.cout * es;
-    a.in_bytes = (int)std::min<long>((long)nr * roi_bytes, kMaxDesc);   // (unused: per-tile descriptors)
-    const long rows = (long)nr * HPP - HP;
-    // BN 256 with a 2-stage weight ring measured faster than BN 128 with 4
-    // stages for conv 1 / 2 (89 / 233 us vs 92 / 256 us at 64 ROIs): the
-    // wider tile halves the weight bytes per MFMA; conv 3 has 64 outputs
-    const int bn = fin ? 64 : (a.cout % 256 == 0 ? 256 : 128);
-    // BN 256: 224-row tiles when that packs the rounds of one workgroup per
-    // CU better (64 ROIs: 961 tiles = 4 rounds of 224 rows instead of 841 =
-    // 4 rounds of 256, the last one 29 % full)
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-        ncu = 256;
-    }
-    static const int bm_env = kpd_diag_env("KPD_HMCONV_BM") ? atoi(kpd_diag_env("KPD_HMCONV_BM")) : 0;   // A/B
-    auto cost = [&](long bm) { return ((rows + bm - 1) / bm * (a.cout / bn) + ncu - 1) / ncu * bm; };
-    // conv 1 / 2 (cin 64 / 256) always take 224-row tiles: those are the
-    // instances with the input channels as a compile-time constant (the
-    // generic runtime-cin kernel ran conv 1 + 2 at 640 ROIs (C3) ~2x slower),
-    // and conv 2's tail launch packs the last round
-    const bool spec = a.cin == 64 || a.cin == 256;
-    const int bm = fin || bn != 256 ? BM
-                   : bm_env == 224 || bm_env == BM ? bm_env
-                   : (spec || cost(224) < cost(BM)) ? 224 : BM;
-    const dim3 grid((unsigned)(((rows + bm - 1) / bm) * (a.cout / bn)));
-    static const int dbg = kpd_diag_env("KPD_HMCONV_DBG") ? atoi(kpd_diag_env("KPD_HMCONV_DBG")) : 0;   // ablations only
-    static const int hm_tps = kpd_diag_env("KPD_HM3_TPS1") ? -1 : 0;   // A/B: conv 3 with one tap per K-step
-    static const bool hm_db = kpd_diag_env("KPD_HM3_NODB") == nullptr;  // A/B: conv 3 single fragment set
-    static const bool hm_stagger = kpd_diag_env("KPD_HM_NOSTAGGER") == nullptr;   // A/B: staggered DMA issue (split)
-    a.stagger = hm_stagger ? 1 : 0;
-#define HMK(...) hipLaunchKernelGGL((hmconv_kernel<__VA_ARGS__>), grid, dim3(NT), 0, st, a)
-    // conv 3 (BN 64, one tile per CU round): the rounds after the last full
-    // one would run a partial round of 256-row tiles (64 ROIs: 841 tiles =
-    // 3.3 rounds, the 4th 29 % full).  Instead the full rounds take 256-row
-    // tiles and the rest goes out as 128-row tiles in one extra launch
-    // (146 at 64 ROIs: a half-length round).  Tile sizes never change the
-    // arithmetic of a row (same K order), so results are unchanged.
-    static const bool no_tail = kpd_diag_env("KPD_HM3_NOTAIL") != nullptr;   // A/B
-    // A/B (KPD_HM3_NW4=1): conv 3 split as 4 waves of 64 x 64 -- 1.5x fewer LDS
-    // bytes per MFMA, but one wave per SIMD hides no latency: 0.204 vs 0.173 ms
-    static const bool hm3_nw4 = kpd_diag_env("KPD_HM3_NW4") != nullptr;
-    a.m_off = 0;
-    // one launch for the full rounds and the tail round, the first round
-    // mixing both tile heights (hmconv_mixed_kernel).  Same-box A/B (round 4,
-    // 64 ROIs): conv 1 178 / 180 vs 183 / 182 us (it had no tail launch, so
-    // it also gains the tail tiles' packing), conv 2 502 / 504 vs 500 / 500,
-    // conv 3 182 / 185 vs 178 / 174 -- on for conv 1 only (KPD_HM_MIX=0: off,
-    // 2: conv 2 / conv 3 too)
-    static const int mix_env = kpd_diag_env("KPD_HM_MIX") ? atoi(kpd_diag_env("KPD_HM_MIX")) : 1;
-    const bool no_mix = mix_env == 0 || (mix_env == 1 && a.cin != 64);
-    auto mix_ok = [&](long F, long H) { return !no_mix && ncu % 8 == 0 && F >= ncu && H > 0 && H <= ncu; };
-    auto mix_set = [&](HmConvArgs& m, long F, long H, dim3& g) {
-      m.mix_F = (int)F;
-      m.mix_H = (int)((H + 7) / 8 * 8);   // a share per XCD; tiles past the rows return at once
-      m.mix_lead = ncu / 16;              // half of each XCD's CUs start with a tail tile
-      g = dim3((unsigned)(m.mix_F + m.mix_H));
-    };
-    if (fin && !dbg && !no_tail && !a.stamps && (!split || (a.cin == 256 && hm_db))) {
-      const long nfull = rows / BM, F = nfull / ncu * ncu, rem = rows - F * BM, H = (rem + 127) / 128;
-      if (split && mix_ok(F, H)) {
-        HmConvArgs m = a;
-        dim3 g;
-        mix_set(m, F, H, g);
-        hipLaunchKernelGGL((hmconv_mixed_kernel<64, 2, BM, 128, 256, 3, true, -1>), g, dim3(NT), 0, st, m);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-      if (F > 0 && H > 0 && H <= ncu) {
-        const dim3 g1((unsigned)F), g2((unsigned)H);
-        HmConvArgs a2 = a;
-        a2.m_off = (int)(F * BM);
-        if (split && hm3_nw4) {
-          hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, BM, true, 256, 3, true, 4>), g1, dim3(256), 0, st, a);
-          hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, 128, true, 256, 3, true, 4>), g2, dim3(256), 0, st, a2);
-        } else if (split) {
-          hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, BM, true, 256, 3, true>), g1, dim3(NT), 0, st, a);
-          hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, 128, true, 256, 3, true>), g2, dim3(NT), 0, st, a2);
-        } else {
-          hipLaunchKernelGGL((hmconv_kernel<64, 4>), g1, dim3(NT), 0, st, a);
-          hipLaunchKernelGGL((hmconv_kernel<64, 4, 0, 128>), g2, dim3(NT), 0, st, a2);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    // conv 2 (split, 224-row tiles): complete rounds of 224-row tiles, then
-    // the remaining rows as 192-row tiles in a second launch when they fit
-    // one round (64 ROIs: 768 + 225 tiles instead of 961, the last round
-    // 0.86 as long): 0.528 -> 0.515 ms.  Conv 1 (18 K-steps a tile, so the
-    // per-tile prologue / epilogue dominate) measured 2 % slower with it.
-    // Same K order per row: results unchanged.
-    static const bool no_tail12 = kpd_diag_env("KPD_HM12_NOTAIL") != nullptr;   // A/B
-#if KPD_DIAG
-    // A/B (KPD_HM_PERSIST=1): conv 1 / conv 2 persistent (hmconv_persist_kernel:
-    // each tile's successor prologue issued under its epilogue).  Same-box
-    // (round 4, 64 ROIs): conv 1 0.206 vs 0.174 ms, conv 2 0.503 vs 0.504 ms
-    // -- not on by default
-    static const int persist_env = kpd_diag_env("KPD_HM_PERSIST") ? atoi(kpd_diag_env("KPD_HM_PERSIST")) : 0;
-    if (split && !fin && bn == 256 && bm == 224 && a.cout == 256 && (a.cin == 64 || a.cin == 256) && !dbg &&
-        !a.stamps && persist_env) {
-      const long F = rows / 224 / ncu * ncu, rem = rows - F * 224, H = (rem + 191) / 192;
-      if (F > 0 && H <= ncu && F + H < 0x7fffffffL / 224) {
-        HmConvArgs m = a;
-        m.mix_F = (int)F;
-        m.mix_H = (int)H;
-        if (a.cin == 64) hipLaunchKernelGGL((hmconv_persist_kernel<64>), dim3((unsigned)ncu), dim3(NT), 0, st, m);
-        else hipLaunchKernelGGL((hmconv_persist_kernel<256>), dim3((unsigned)ncu), dim3(NT), 0, st, m);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-#endif
-    // tail tiles of conv 1 / conv 2: 160 rows when those fit one round (the
-    // last round then runs 160-row instead of 192-row tiles), else 192
-    const long F12 = rows / 224 / ncu * ncu, rem12 = rows - F12 * 224;
-    const bool t160 = (rem12 + 159) / 160 <= ncu;
-    const long H12 = t160 ? (rem12 + 159) / 160 : (rem12 + 191) / 192;
-    if (split && !fin && bn == 256 && bm == 224 && (a.cin == 64 || a.cin == 256) && !dbg && !a.stamps) {
-      if (mix_ok(F12, H12)) {   // conv 1 / conv 2
-        HmConvArgs m = a;
-        dim3 g;
-        mix_set(m, F12, H12, g);
-        if (a.cin == 64 && t160) hipLaunchKernelGGL((hmconv_mixed_kernel<256, 2, 224, 160, 64, 1, false, -1>), g, dim3(NT), 0, st, m);
-        else if (a.cin == 64) hipLaunchKernelGGL((hmconv_mixed_kernel<256, 2, 224, 192, 64, 1, false, -1>), g, dim3(NT), 0, st, m);
-        else if (t160) hipLaunchKernelGGL((hmconv_mixed_kernel<256, 2, 224, 160, 256, 1, false, -1>), g, dim3(NT), 0, st, m);
-        else hipLaunchKernelGGL((hmconv_mixed_kernel<256, 2, 224, 192, 256, 1, false, -1>), g, dim3(NT), 0, st, m);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-    if (split && !fin && bn == 256 && bm == 224 && a.cin == 256 && !dbg && !no_tail12 && !a.stamps) {
-      if (F12 > 0 && rem12 > 0 && H12 <= ncu) {
-        const dim3 g1((unsigned)F12), g2((unsigned)H12);
-        HmConvArgs a2 = a;
-        a2.m_off = (int)(F12 * 224);
-        hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224, true, 256>), g1, dim3(NT), 0, st, a);
-        if (t160) hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 160, true, 256>), g2, dim3(NT), 0, st, a2);
-        else hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 192, true, 256>), g2, dim3(NT), 0, st, a2);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        continue;
-      }
-    }
-#if KPD_DIAG
-    if (split && dbg) {   // ablations (KPD_HMCONV_DBG=1: no MFMA, 2: no K-loop DMA); wrong results by design
-      if (fin && dbg == 1) HMK(64, 2, 1, BM, true, 256, 3, true);   // the production conv 3 variant
-      else if (fin) HMK(64, 2, 2, BM, true, 256, 3, true);
-      else if (dbg == 1) HMK(256, 2, 1, 224, true, 256);
-      else HMK(256, 2, 2, 224, true, 256);
-    } else
-#endif
-    if (split) {
-      if (fin && a.cin == 256 && hm_db && hm3_nw4)
-        hipLaunchKernelGGL((hmconv_kernel<64, 2, 0, BM, true, 256, 3, true, 4>), grid, dim3(256), 0, st, a);
-      else if (fin && a.cin == 256 && hm_db) HMK(64, 2, 0, BM, true, 256, 3, true);
-      else if (fin && a.cin == 256 && !(hm_tps < 0)) HMK(64, 2, 0, BM, true, 256, 3);
-      else if (fin && a.cin == 256) HMK(64, 4, 0, BM, true, 256);
-      else if (fin) HMK(64, 4, 0, BM, true);
-      else if (bn == 256 && bm == 224 && a.cin == 64) HMK(256, 2, 0, 224, true, 64);
-      else if (bn == 256 && bm == 224 && a.cin == 256) HMK(256, 2, 0, 224, true, 256);
-      else if (bn == 256 && bm == 224) HMK(256, 2, 0, 224, true);
-      else if (bn == 256) HMK(256, 2, 0, BM, true);
-      else HMK(128, 4, 0, BM, true);
-    } else if (fin) hipLaunchKernelGGL((hmconv_kernel<64, 4>), grid, dim3(NT), 0, st, a);
-    else if (bn == 256 && bm == 224 && dbg == 0 && a.cin == 64) HMK(256, 2, 0, 224, false, 64);
-    else if (bn == 256 && bm == 224 && dbg == 0 && a.cin == 256) HMK(256, 2, 0, 224, false, 256);
-    else if (bn == 256 && bm == 224 && dbg == 0) hipLaunchKernelGGL((hmconv_kernel<256, 2, 0, 224>), grid, dim3(NT), 0, st, a);
-#if KPD_DIAG
-    else if (bn == 256 && dbg == 1) hipLaunchKernelGGL((hmconv_kernel<256, 2, 1>), grid, dim3(NT), 0, st, a);
-    else if (bn == 256 && dbg == 2) hipLaunchKernelGGL((hmconv_kernel<256, 2, 2>), grid, dim3(NT), 0, st, a);
-#endif
-    else if (bn == 256) hipLaunchKernelGGL((hmconv_kernel<256, 2>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((hmconv_kernel<128, 4>), grid, dim3(NT), 0, st, a);
-#undef HMK
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
   }
-  return hipSuccess;
+  // bytes per channel: bf16, or f16 hi + lo; the GEMM row index stays a 32-bit int
+  const long wt_bytes = (long)a0.cout * (kh ? a0.ntap : 9) * a0.cin * (split ? 4 : 2);
+  if (wt_bytes > kMaxDesc || (long)a0.R * HPP >= 0x7fffffffL) return hipErrorInvalidValue;
+  const HmKnobs& k = hm_knobs();
+  HmConvArgs a = a0;
+  a.wt_bytes = (int)wt_bytes;
+  a.stagger = kh ? k.kh_stagger : linear ? split : k.stagger;
+  if (linear) {
+    a.r0 = 0;
+    a.out_idx = -1;
+    a.amax_idx = -1;
+  }
+  const HmSchedule s = hm_schedule(a, kpd_num_cus(), k);
+  for (int i = 0; i < s.n; ++i) hm_launch(s.l[i], a, st);
+  return hipGetLastError();
 }
 
 hipError_t launch_fpn0x(const Fpn0xArgs& a, hipStream_t st) {
@@ -2530,13 +2270,7 @@ hipError_t launch_fpn0x(const Fpn0xArgs& a, hipStream_t st) {
   if ((long)a.N * a.Hf * a.Wf * 512 >= (1L << 31) || (long)a.N * 16 * a.tpc * 1024 >= (1L << 31))
     return hipErrorInvalidValue;
   // persistent: one workgroup per CU (the kernel walks the slots in epochs)
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = kpd_num_cus();
   // slots of 1-3 per-class tiles: 8 per (image, row block), or 10 shorter ones while those fit one epoch
   const int spn = 10L * a.N * a.tpc <= ncu ? 10 : 8;
   const long tiles = (long)spn * a.N * a.tpc;

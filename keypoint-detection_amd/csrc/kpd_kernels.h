@@ -4,6 +4,19 @@
 #include <stdint.h>
 #include <vector>
 
+// Compute units of the current device, queried once (thread-safe: a
+// function-local static); 256 when the query fails.
+inline int kpd_num_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return ncu;
+}
+
 struct ConvArgs {
   const void* in;        // NHWC [N][H][W][in_cstride] (TA)
   const void* wt;        // [cout_p][KS*KS][cin_p] (TA), BN folded
@@ -80,10 +93,10 @@ struct HmConvArgs {
   const int32_t* slot;
   int P;
   float* heat;
-  int r0;                // first ROI of the launch chunk (launcher)
-  int m_off;             // launcher: first GEMM row of tile 0 (tail launch of conv 3)
+  int r0;                // global index of the launch's first ROI (hsc / slot rows; linear mode: launcher sets 0)
+  int m_off;             // launcher: first GEMM row of tile 0 (tail launches)
   int mix_F, mix_H, mix_lead;   // launcher: hmconv_mixed_kernel's full / tail tile counts, lead pairs per XCD
-  int in_bytes, wt_bytes;   // launcher
+  int in_bytes, wt_bytes;   // in_bytes: unused (per-tile input descriptors), kept for the layout; wt_bytes: launcher
   int stagger;              // launcher: split K loop, waves 4-7 issue their DMA one pass later
   unsigned long long* stamps;   // diagnostic phase stamps [grid][8] (KPD_STAMPS), normally null
   // KEYPOINT_HEAD mode (kh_ps != null; split only): wt is [cout][ntap][cin] with

@@ -1170,8 +1170,8 @@ static int stage_heads(Pass& ps, const FwdArgs& a, bool roi_kh) {
     HIP_TRY(launch_roi_align(w.feat, ps.d.Hf, ps.d.Wf, 128, nullptr, a.boxes, R, P, w.kx, nullptr, st));
   }
   kpd_path_at(KP_KH);
-  // sized for 256-row tiles, the smallest launch_hmconv_kh picks (KPD_KH_BM256 /
-  // KPD_KH_TPS1 take them for every conv; by default convs 2 / 3 use 384 / 512)
+  // sized for 256-row tiles, the smallest the KEYPOINT_HEAD convs take (hm_schedule,
+  // conv_glds.hip: conv 1 256 rows, convs 2 / 3 384 / 512)
   unsigned long long* khst[3] = {ps.take_stamps("stamps_kh1", (size_t)((hmrows + 255) / 256)),
                                  ps.take_stamps("stamps_kh2", (size_t)((hmrows + 255) / 256)),
                                  ps.take_stamps("stamps_kh3", (size_t)((hmrows + 255) / 256))};
