@@ -576,6 +576,32 @@ int kpd_coord_loss(const float* heat, const float* gt, const float* vis, int pla
 int kpd_softargmax_backward(const float* heat, const float* grad_coords, int planes, int H, int W, float temperature,
                             float* grad_heat, void* stream);
 
+/* The backward of the forward's ROI align onto FPN level 0:
+ * what trains the FPN neck under the heatmap head.  gout [n][Cs][56][56] =
+ * dL / d(ROI features) of the rows `rows` (n ascending indices into B*P, int32,
+ * device) of boxes [B][P][4] (cxcywh, normalised: the forward's); topk
+ * [B][Cs] int32 (device) = the distinct level-0 channels of image b that the
+ * Cs feature channels were gathered from, or NULL for Cs == C in order.
+ * A box becomes a ROI exactly as kpd_roi_features makes it: corners clamped to
+ * [0, 1] and scaled by W, H, extent at least 1, aligned=False, sampling grid
+ * ceil(extent / 56), the sample coordinates in fp32 in torchvision's
+ * expression order without contraction and the skip / clamp decisions taken
+ * on them.  gfeat [B][C][H][W] (NCHW) = dL / d(level 0) is written completely
+ * and every element exactly once: a ROI's channel s lands in channel
+ * topk[b][s], the ROIs of an image are summed in ascending row order, and
+ * pixels no ROI touches, channels topk[b] does not name and images without a
+ * row are zeros -- no memset before the call.  No floating-point atomics: two
+ * calls give the same bits, and an image's gradient depends on its own rows
+ * only, not on what shares the call.  n = 0 is legal (all zeros).  Arguments
+ * are checked before any device work (KPD_EINVAL: n > B*P, Cs > C, Cs != C
+ * without topk, a null gout / boxes / rows with n > 0, a null gfeat, a map too
+ * wide for the workgroup's LDS tables: W up to about 550, any H); rows outside
+ * [0, B*P), or not ascending, and repeated topk entries are the caller's
+ * contract (such rows are ignored or summed in an unspecified order; nothing
+ * is read or written out of bounds).  No scratch, no host synchronisation. */
+int kpd_roi_align_backward(const float* gout, const float* boxes, const int32_t* rows, int n, int B, int P,
+                           const int32_t* topk, int Cs, int C, int H, int W, float* gfeat, void* stream);
+
 /* Concurrency: a forward pass over B >= 32 images runs as min(n, B/16)
  * contiguous sub-batches on as many streams (forked from / joined back into
  * the caller's stream), so the latency-bound small launches of one sub-batch

@@ -36,7 +36,8 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_plan_path_log", "kpd_plan_path_query", "kpd_preprocess_batch", "kpd_draw_poses",
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
            "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features", "kpd_detector_features",
-           "kpd_detector_targets", "kpd_detector_loss", "kpd_coord_loss", "kpd_softargmax_backward")
+           "kpd_detector_targets", "kpd_detector_loss", "kpd_coord_loss", "kpd_softargmax_backward",
+           "kpd_roi_align_backward")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -185,6 +186,7 @@ def load() -> ctypes.CDLL:
     lib.kpd_detector_loss.argtypes = [c_void_p] * 9 + [c_int] * 4 + [c_float] * 4 + [c_void_p] * 6
     lib.kpd_coord_loss.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_float, c_float] + [c_void_p] * 4
     lib.kpd_softargmax_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]
+    lib.kpd_roi_align_backward.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] + [c_int] * 4 + [c_void_p] * 2
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
@@ -881,4 +883,39 @@ def softargmax_backward(heat: torch.Tensor, grad_coords: torch.Tensor, temperatu
     with torch.cuda.device(heat.device):
         check(load().kpd_softargmax_backward(_ptr(heat), _ptr(g), n * K, H, W, t, _ptr(out), _stream(heat.device)),
               "kpd_softargmax_backward")
+    return out
+
+
+def roi_align_backward(grad_out: torch.Tensor, boxes: torch.Tensor, rows, topk: Optional[torch.Tensor],
+                       channels: int, height: int, width: int) -> torch.Tensor:
+    """kpd_roi_align_backward: grad_out [n,Cs,56,56] = dL / d(ROI features) of the
+    rows ``rows`` (ascending indices into B*P; None = all) of boxes [B,P,4]
+    (cxcywh, normalised), topk [B,Cs] (the level-0 channels the features were
+    gathered from; None: Cs == channels, in order) -> dL / d(level 0)
+    [B,channels,height,width], written completely by the call (zeros where
+    nothing lands).  Deterministic; no host synchronisation."""
+    g = _dev_f32(grad_out.detach(), "grad_out")
+    dev = g.device
+    boxes = _dev_f32(boxes.detach(), "boxes").to(dev)
+    if boxes.dim() != 3 or boxes.size(2) != 4:
+        raise ValueError(f"boxes must be [B, P, 4], got {tuple(boxes.shape)}")
+    B, P = boxes.shape[:2]
+    rows = _row_list(rows, dev)
+    n = B * P if rows is None else rows.numel()
+    if rows is None:
+        rows = torch.arange(n, dtype=torch.int32, device=dev)
+    if g.dim() != 4 or g.size(0) != n or tuple(g.shape[2:]) != (56, 56):
+        raise ValueError(f"grad_out must be [{n}, Cs, 56, 56], got {tuple(g.shape)}")
+    Cs, C, H, W = g.size(1), int(channels), int(height), int(width)
+    if topk is not None:
+        _require_cuda(topk, "topk")
+        if topk.is_floating_point() or tuple(topk.shape) != (B, Cs):
+            raise ValueError(f"topk must be an integer tensor [{B}, {Cs}], got {tuple(topk.shape)}")
+        topk = topk.to(dev, torch.int32).contiguous()
+    out = torch.empty(B, C, H, W, device=dev)
+    with torch.cuda.device(dev):
+        check(load().kpd_roi_align_backward(_ptr(g) if n else None, _ptr(boxes) if n else None,
+                                            _ptr(rows) if n else None, n, B, P, _ptr(topk), Cs, C, H, W,
+                                            _ptr(out) if out.numel() else None, _stream(dev)),
+              "kpd_roi_align_backward")
     return out

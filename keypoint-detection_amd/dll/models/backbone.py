@@ -16,10 +16,13 @@ oracle/kpd_oracle.py:MBV3_SMALL_BNECK.
 from collections import OrderedDict
 from typing import List
 
+import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _native
 from ..configs.model_config import BackboneConfig
+from ..ops import bn_relu_dropout2d, conv3x3
 
 # (in, kernel, expanded, out, use_se, activation, stride) -- torchvision table
 MBV3_SMALL_BNECK = (
@@ -108,6 +111,46 @@ class LightweightFPN(nn.Module):
         if self.training:
             raise NotImplementedError("the FPN runs the eval path only; call .eval()")
         return self._plans.get(self, features[0].device, "fp32").fpn(list(features))
+
+    def forward_level0(self, features, precision: str = "split"):
+        """FPN level 0 [B,128,h_0,w_0] of the four taps, differentiable with
+        respect to the parameters on its path -- the four lateral convolutions
+        and ``fpn_convs[0]`` -- in ``train()`` and in ``eval()`` mode: the
+        heatmap path's share of ``forward`` (reference backbone.py:33-39), which
+        ``Trainer(train_neck=True)`` trains.  The laterals and
+        the nearest-neighbour top-down sums are torch ops; the 3x3 convolution
+        is ``dll.ops.conv3x3`` in ``precision`` ("split" | "mixed"); in train
+        mode the batch norm takes batch statistics and updates the running ones
+        (``dll.ops.bn_relu_dropout2d``), in eval mode it uses the running ones.
+        ``fpn_convs[1..3]`` are not on this path and are not read."""
+        if len(features) != len(self.lateral_convs):
+            raise ValueError(f"Expected {len(self.lateral_convs)} features, got {len(features)}")
+        _native._require_cuda(features[0], "features[0]")
+        top = None
+        for conv, f in zip(reversed(self.lateral_convs), reversed(list(features))):
+            # the 1x1 convolution as a matmul: the framework's own convolution backward is not
+            # bit-reproducible from run to run on the device, a matmul's is (as in SpatialAttention)
+            f = f.float()
+            lat = torch.matmul(conv.weight.flatten(1), f.flatten(2)).view(f.size(0), -1, f.size(2), f.size(3))
+            top = lat if top is None else lat + F.interpolate(top, size=lat.shape[2:], mode="nearest")
+        conv, bn = self.fpn_convs[0][0], self.fpn_convs[0][1]
+        x = conv3x3(top, conv.weight, None, precision=precision)
+        if not self.training:
+            return F.relu(F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps))
+        momentum = 0.0 if bn.momentum is None else bn.momentum
+        if bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+            if bn.momentum is None:   # cumulative moving average
+                momentum = 1.0 / float(bn.num_batches_tracked)
+        return bn_relu_dropout2d(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
+                                 bn.running_var if bn.track_running_stats else None, momentum=momentum, eps=bn.eps,
+                                 relu=True, drop=None)
+
+    # the parameters forward_level0 reads, as named under ``backbone.fpn.`` (what train_neck optimises)
+    LEVEL0_PARAMETERS = ("lateral_convs.0.weight", "lateral_convs.1.weight", "lateral_convs.2.weight",
+                         "lateral_convs.3.weight", "fpn_convs.0.0.weight", "fpn_convs.0.1.weight",
+                         "fpn_convs.0.1.bias")
+    LEVEL0_BUFFERS = ("fpn_convs.0.1.running_mean", "fpn_convs.0.1.running_var", "fpn_convs.0.1.num_batches_tracked")
 
     def __init__(self, in_channels_list, out_channels):
         super().__init__()

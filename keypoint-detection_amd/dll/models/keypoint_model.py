@@ -28,6 +28,7 @@ from .. import _native
 from ..configs.model_config import ModelConfig
 from ..configs.training_config import TrainingConfig
 from ..losses import KeypointLoss
+from ..ops import roi_align_boxes
 from .backbone import MobileNetV3Wrapper
 from .heatmap_head import HeatmapHead
 from .keypoint_head import KEYPOINT_HEAD
@@ -415,3 +416,29 @@ class MultiPersonKeypointModel(nn.Module):
     def _soft_argmax(self, heatmap: torch.Tensor) -> torch.Tensor:
         """E[x] / (W - 1), E[y] / (H - 1) under softmax over each map (reference :284-313)."""
         return _native.decode_heatmaps(heatmap, _native.DECODE_SOFTARGMAX, 1.0)[0]
+
+
+def neck_roi_features(model: MultiPersonKeypointModel, image: torch.Tensor, boxes: torch.Tensor, rows: torch.Tensor,
+                      precision: str = "split", return_parts: bool = False):
+    """The heatmap head's input [n,64,56,56] for the rows ``rows`` (ascending
+    indices into B*P, int32 device tensor) of boxes [B,P,4], computed so that a
+    gradient reaches the FPN's level-0 path -- the function
+    ``Plan.roi_features`` computes, in differentiable pieces:
+
+        taps   = model.backbone.body(image)            native, frozen, under no_grad
+        level0 = model.backbone.fpn.forward_level0(taps, precision)
+        topk   = channel_attention top-64 of level0    native, frozen, no gradient (the reference's neither)
+        x      = dll.ops.roi_align_boxes(level0, boxes, rows, topk)
+
+    It does not go through ``model.native_plan``: that plan's key includes the
+    FPN weights, which change with every training step; the body's own plan is
+    keyed on the body's weights only.  With ``return_parts``: (x, topk [B,64]
+    int64, level0 [B,128,h,w])."""
+    image = image.float().contiguous()
+    with torch.no_grad():
+        taps = list(model.backbone.body(image).values())
+    level0 = model.backbone.fpn.forward_level0(taps, precision)
+    with torch.no_grad():
+        topk = model.channel_attention.native_select(level0.detach(), 64, select=False)[1]
+    x = roi_align_boxes(level0, boxes, rows, topk)
+    return (x, topk, level0) if return_parts else x

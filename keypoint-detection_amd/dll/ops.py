@@ -41,6 +41,14 @@ heatmaps in the same pass:
     from dll.ops import soft_argmax, soft_argmax_coord_loss
     coords = soft_argmax(heat, temperature=1.0)                  # == decode_heatmaps_soft_argmax(heat)[0]
     loss, coords = soft_argmax_coord_loss(heat, gt_coords, visibility)
+
+and the ROI align between FPN level 0 and the heatmap head as a differentiable
+op (libkpd: kpd_roi_align forward, kpd_roi_align_backward, DESIGN.md §3l: a
+deterministic gather, no floating-point atomics), which is what lets
+``Trainer(train_neck=True)`` train the FPN's level-0 path under the head:
+
+    from dll.ops import roi_align_boxes
+    x = roi_align_boxes(level0, boxes, rows, topk)   # [n, Cs, 56, 56]; gradient to level0 only
 """
 from __future__ import annotations
 
@@ -245,3 +253,81 @@ def soft_argmax_coord_loss(heat: torch.Tensor, gt_coords: torch.Tensor, visibili
     synchronisation."""
     return SoftArgmaxCoordLossFunction.apply(heat, gt_coords, visibility, float(temperature), str(loss_type),
                                              float(pixel_weight_scale), float(distance_threshold))
+
+
+def boxes_to_rois(boxes: torch.Tensor, rows: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """The rows ``rows`` of cxcywh boxes [B, P, 4] as roi_align rois [n, 5] (image,
+    x1, y1, x2, y2) on a height x width map, by the fused forward's rule
+    (kpd_roi_features): corners clamped to [0, 1], then scaled, in fp32."""
+    r = rows.long()
+    b = boxes.reshape(-1, 4).float()[r]
+    half = b[:, 2:] / 2
+    scale = torch.tensor([width, height], dtype=torch.float32, device=b.device)
+    lo = torch.clamp(b[:, :2] - half, 0, 1) * scale
+    hi = torch.clamp(b[:, :2] + half, 0, 1) * scale
+    image = torch.div(r, boxes.size(1), rounding_mode="floor").to(torch.float32)
+    return torch.cat([image[:, None], lo, hi], dim=1)
+
+
+class RoiAlignBoxesFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, level0, boxes, rows, topk):
+        B, C, H, W = level0.shape
+        rois = boxes_to_rois(boxes, rows, H, W)
+        if topk is None:
+            out = _native.roi_align(level0, rois, 56)
+        else:
+            # x[b, topk[b]] as B * Cs single-channel images, and every ROI once per channel on its own
+            # image's Cs planes: one kpd_roi_align call whatever topk holds.  This is a detour off the
+            # fused forward's path, paid for simplicity: the gather materialises a [B, Cs, H, W] copy
+            # (201 MB at 64 x 64 x 128 x 96) and the per-ROI coordinate work is repeated Cs times; top-k +
+            # this forward measure 0.68 ms of a 35.7 ms step (DESIGN.md §7 Round 19).  A channel-indexed
+            # forward kernel would avoid both.
+            Cs = topk.size(1)
+            sel = torch.gather(level0.detach().float(), 1, topk.long()[:, :, None, None].expand(B, Cs, H, W))
+            n = rois.size(0)
+            planes = (rois[:, :1] * Cs + torch.arange(Cs, device=rois.device, dtype=torch.float32)[None, :])
+            per_plane = torch.cat([planes.reshape(-1, 1), rois[:, None, 1:].expand(n, Cs, 4).reshape(-1, 4)], dim=1)
+            out = _native.roi_align(sel.reshape(B * Cs, 1, H, W), per_plane, 56).view(n, Cs, 56, 56)
+        ctx.save_for_backward(boxes, rows, topk if topk is not None else torch.empty(0, device=level0.device))
+        ctx.shape, ctx.has_topk, ctx.dtype = (C, H, W), topk is not None, level0.dtype
+        return out.to(level0.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: torch.Tensor):
+        boxes, rows, topk = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        g = _native.roi_align_backward(grad_out, boxes, rows, topk if ctx.has_topk else None, *ctx.shape)
+        return g.to(ctx.dtype), None, None, None
+
+
+def roi_align_boxes(level0: torch.Tensor, boxes: torch.Tensor, rows: torch.Tensor,
+                    topk: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ROI align of FPN level 0 [B, C, H, W] over the rows ``rows`` (ascending
+    indices into B*P, an integer device tensor) of cxcywh boxes [B, P, 4], as the
+    fused forward does it (56 x 56 bins, aligned=False, adaptive sampling grid),
+    on the channels ``topk`` [B, Cs] of each ROI's image (None: all C) ->
+    [n, Cs, 56, 56], differentiable with respect to ``level0``: the forward is
+    kpd_roi_align on x[b, topk[b]], the backward kpd_roi_align_backward
+    (deterministic, no atomics).  boxes, rows and topk get no
+    gradient.  Device tensors only; no host synchronisation."""
+    _native._require_cuda(level0, "level0")
+    if level0.dim() != 4:
+        raise ValueError(f"level0 must be [B, C, H, W], got {tuple(level0.shape)}")
+    B = level0.size(0)
+    if boxes.dim() != 3 or boxes.size(0) != B or boxes.size(2) != 4:
+        raise ValueError(f"boxes must be [{B}, P, 4], got {tuple(boxes.shape)}")
+    if rows.dim() != 1 or rows.is_floating_point():
+        raise ValueError("rows must be a 1-D integer tensor")
+    if rows.numel() > B * boxes.size(1):
+        raise ValueError(f"rows holds {rows.numel()} indices for {B * boxes.size(1)} boxes")
+    if topk is not None and (topk.dim() != 2 or topk.size(0) != B or topk.is_floating_point()
+                             or topk.size(1) > level0.size(1)):
+        raise ValueError(f"topk must be an integer tensor [{B}, Cs <= {level0.size(1)}], got {tuple(topk.shape)}")
+    dev = level0.device
+    boxes = boxes.detach().to(dev, torch.float32).contiguous()
+    rows = rows.detach().to(dev, torch.int32).contiguous()
+    topk = None if topk is None else topk.detach().to(dev, torch.int32).contiguous()
+    return RoiAlignBoxesFunction.apply(level0, boxes, rows, topk)

@@ -10,7 +10,8 @@ driving the native pieces of a top-down training step:
     loss  += coord_weight * coord_loss(heat, joints in the ROI frame, tw)   coord_weight > 0: kpd_coord_loss
     loss.backward(); optimizer.step()
 
-Only ``model.heatmap_head`` is trained: the optimizer holds its parameters and
+With ``train_neck=False`` (the default) only ``model.heatmap_head`` is trained:
+the optimizer holds its parameters and
 nothing else, the rest of the model stays in eval mode, and every epoch ends
 with a check that no state tensor outside ``heatmap_head.`` changed.  The
 trunk plan is taken from ``model.native_plan(device)`` once per epoch: its
@@ -44,9 +45,34 @@ the step keeps its one synchronisation).  Validation then also reports
 checkpoints are what they were.  Whether the term improves trained accuracy,
 and at which weight or temperature, is unmeasured: no dataset run exists.
 
+``train_neck=True`` trains the FPN's level-0 path with the head (DESIGN.md
+§3l).  The parts of the neck between the pretrained body and the head -- the
+four ``backbone.fpn.lateral_convs`` and ``backbone.fpn.fpn_convs.0`` -- have no
+pretrained weights anywhere, so a head-only run fits the head to a random
+projection.  The step's ``x`` then comes from ``neck_roi_features`` (frozen
+native body taps -> ``fpn.forward_level0`` in train mode -> frozen top-64
+indices -> ``dll.ops.roi_align_boxes``, whose backward is the deterministic
+kpd_roi_align_backward) instead of the plan, and the optimizer gets a second
+parameter group at ``learning_rate * neck_lr_scale`` holding exactly
+``backbone.fpn.lateral_convs.{0,1,2,3}.weight``, ``fpn_convs.0.0.weight`` and
+``fpn_convs.0.1.{weight,bias}``.  ``backbone.fpn`` is in train mode for the
+step and back in eval mode at the epoch's end; the frozen-state check then
+allows those seven tensors and the batch norm's three buffers to change and
+still covers everything else: the body, ``channel_attention`` (the top-k has no
+gradient), ``fpn_convs.1..3`` (not on the heatmap path), the person head.
+``use_amp=True`` also runs the level-0 convolution on bf16 operands.
+Validation is unchanged: the eval head on the plan's features, the plan
+re-taken per epoch and so re-packed from the new FPN weights and statistics.
+Checkpoints keep their format; the optimizer state has one more group, so
+``resume`` into a trainer with the other ``train_neck`` setting raises.  What
+follows from moving level 0: the person detector and KEYPOINT_HEAD read level
+0 too, so a detector trained (``DetectorTrainer``) before a neck run must be
+retrained after it.  Accuracy stays unmeasured: no dataset run exists.
+
 Out of scope: the visibility term (the head's visibility is a threshold on the
 map's maximum and has no gradient), DynamicLossBalancer, coordinate
-supervision of the detector or KEYPOINT_HEAD, training the trunk or
+supervision of the detector or KEYPOINT_HEAD, training the body,
+``channel_attention`` (a differentiable top-k), FPN levels 1-3 or
 KEYPOINT_HEAD (the person detector has its own trainer, ``DetectorTrainer``
 in detector_trainer.py, DESIGN.md §3j;
 joint detector + head steps are out of scope of both), ``torch.autocast`` /
@@ -67,11 +93,13 @@ from torch.optim import lr_scheduler
 from ..configs.training_config import TrainingConfig
 from ..losses.keypoint_loss import SoftArgmaxCoordinateLoss
 from ..models.heatmap_head import decode_heatmaps, generate_roi_targets
+from ..models.keypoint_model import neck_roi_features
 from ..utils.metric import _metrics_on_device
 
 logger = logging.getLogger(__name__)
 
 HEAD_PREFIX = "heatmap_head."
+NECK_PREFIX = "backbone.fpn."
 TARGET_SIGMA = 2.0   # the reference's _convert_keypoints_to_heatmaps
 
 
@@ -87,7 +115,8 @@ def batch_boxes(batch: Dict) -> torch.Tensor:
 class Trainer:
     def __init__(self, model: nn.Module, device: torch.device, train_dataloader, val_dataloader,
                  config: TrainingConfig, output_dir: Optional[Union[str, Path]] = None, use_amp: bool = False,
-                 coord_weight: float = 0.0, coord_temperature: float = 1.0):
+                 coord_weight: float = 0.0, coord_temperature: float = 1.0, train_neck: bool = False,
+                 neck_lr_scale: float = 1.0):
         if not (0.0 <= float(coord_weight) < float("inf")):
             raise ValueError(f"coord_weight must be finite and >= 0, got {coord_weight}")
         if not (0.0 < float(coord_temperature) < float("inf")):
@@ -96,8 +125,16 @@ class Trainer:
             raise NotImplementedError("AMP training runs on the native bf16 kernels of the heatmap head's train path "
                                       "(DESIGN.md §3i), which need a GPU device; construct the Trainer with "
                                       "use_amp=False")
+        if not (0.0 < float(neck_lr_scale) < float("inf")):
+            raise ValueError(f"neck_lr_scale must be positive and finite, got {neck_lr_scale}")
+        if train_neck and torch.device(device).type != "cuda":
+            raise NotImplementedError("train_neck runs the FPN's level-0 path on the native conv3x3, batch-norm and "
+                                      "ROI-align backward kernels (DESIGN.md §3l), which need a GPU device; construct "
+                                      "the Trainer with train_neck=False")
         if not hasattr(model, "heatmap_head"):
             raise TypeError("Trainer trains model.heatmap_head; pass a MultiPersonKeypointModel")
+        if train_neck and not hasattr(getattr(model, "backbone", None), "fpn"):
+            raise TypeError("train_neck trains model.backbone.fpn; pass a MultiPersonKeypointModel")
         self.device = torch.device(device)
         self.model = model.to(self.device)
         self.head = self.model.heatmap_head
@@ -115,6 +152,9 @@ class Trainer:
         self.coord_weight = float(coord_weight)
         self.coord_temperature = float(coord_temperature)
         self.coord_loss_fn = SoftArgmaxCoordinateLoss(self.coord_temperature) if self.coord_weight > 0 else None
+        # the FPN's level-0 path trained with the head (module docstring); False: never touched
+        self.train_neck = bool(train_neck)
+        self.neck_lr_scale = float(neck_lr_scale)
         self.model.eval()
         self.optimizer = self._create_optimizer()
         sc = config.lr_scheduler
@@ -133,6 +173,10 @@ class Trainer:
     def _create_optimizer(self) -> torch.optim.Optimizer:
         oc = self.config.optimizer
         params = list(self.head.parameters())
+        if self.train_neck:   # a second group: exactly the parameters on the level-0 path, at their own rate
+            params = [{"params": params},
+                      {"params": [p for _, p in self.neck_parameters()],
+                       "lr": float(oc.learning_rate) * self.neck_lr_scale}]
         name = str(oc.name).lower()
         if name == "adam":
             return torch.optim.Adam(params, lr=float(oc.learning_rate), betas=(float(oc.beta1), float(oc.beta2)),
@@ -142,9 +186,23 @@ class Trainer:
                                    weight_decay=float(oc.weight_decay))
         raise ValueError(f"Unsupported optimizer: {oc.name}")
 
+    def neck_parameters(self) -> List[Tuple[str, nn.Parameter]]:
+        """(state-dict name, parameter) of the parameters on the FPN's level-0 path, in a fixed order."""
+        fpn = self.model.backbone.fpn
+        named = dict(fpn.named_parameters())
+        return [(NECK_PREFIX + k, named[k]) for k in fpn.LEVEL0_PARAMETERS]
+
+    def _trained_names(self) -> set:
+        """State tensors outside ``heatmap_head.`` that an epoch may change."""
+        if not self.train_neck:
+            return set()
+        fpn = self.model.backbone.fpn
+        return {NECK_PREFIX + k for k in fpn.LEVEL0_PARAMETERS + fpn.LEVEL0_BUFFERS}
+
     def _frozen_versions(self) -> Dict[str, Tuple[int, int]]:
+        free = self._trained_names()
         return {k: (t.data_ptr(), t._version) for k, t in self.model.state_dict(keep_vars=True).items()
-                if not k.startswith(HEAD_PREFIX)}
+                if not k.startswith(HEAD_PREFIX) and k not in free}
 
     def trunk_plan(self):
         """The model's plan, taken once per epoch (module docstring)."""
@@ -153,16 +211,21 @@ class Trainer:
         return self._plan
 
     # ------------------------------------------------------------------ one batch
-    def _features_and_targets(self, batch: Dict):
+    def _features_and_targets(self, batch: Dict, through_neck: bool = False):
         """(x [n,64,56,56], gt [n,K,H,W], tw [n,K], rows [n] int32, boxes [B,P,4]) or None without a
-        labelled box.  The nonzero() below is the step's one host synchronisation."""
+        labelled box.  The nonzero() below is the step's one host synchronisation.  ``through_neck``
+        (the train step of train_neck): x from neck_roi_features, with a gradient to the FPN's level-0
+        path; otherwise the plan's frozen features."""
         image = batch["image"].to(self.device)
         boxes = batch_boxes(batch).to(self.device, torch.float32).contiguous()
         rows = torch.nonzero((boxes != 0).any(dim=-1).flatten()).flatten().to(torch.int32)   # ascending
         if rows.numel() == 0:
             return None
-        with torch.no_grad():
-            x = self.trunk_plan().roi_features(image, boxes, rows)
+        if through_neck:
+            x = neck_roi_features(self.model, image, boxes, rows, "mixed" if self.use_amp else "split")
+        else:
+            with torch.no_grad():
+                x = self.trunk_plan().roi_features(image, boxes, rows)
         kp = batch["keypoints"].to(self.device, torch.float32)
         vis = batch["visibilities"].to(self.device, torch.float32)
         # the head keeps its input's spatial size (config.heatmap_size is unused by it, a reference quirk)
@@ -182,7 +245,9 @@ class Trainer:
         (detached), 'rows': n, 'skipped': bool}; with coord_weight > 0 'loss'
         is the total and 'heatmap_loss' / 'coord_loss' its two parts.  A batch
         without a labelled box is skipped (no step, loss None)."""
-        ft = self._features_and_targets(batch)
+        if self.train_neck:
+            self.model.backbone.fpn.train()
+        ft = self._features_and_targets(batch, through_neck=self.train_neck)
         if ft is None:
             return {"loss": None, "rows": 0, "skipped": True}
         x, gt, tw, rows, boxes = ft
@@ -214,8 +279,11 @@ class Trainer:
             steps += 1
             losses.append(out["loss"])
         self.head.eval()
+        if self.train_neck:
+            self.model.backbone.fpn.eval()
         changed = [k for k, v in self._frozen_versions().items() if before.get(k) != v]
-        assert not changed, f"state outside {HEAD_PREFIX} changed during the epoch: {changed[:5]}"
+        what = f"{HEAD_PREFIX} and the FPN's level-0 path" if self.train_neck else HEAD_PREFIX
+        assert not changed, f"state outside {what} changed during the epoch: {changed[:5]}"
         loss = float(torch.stack(losses).double().mean()) if losses else 0.0
         return {"loss": loss, "steps": steps, "skipped_steps": skipped}
 
@@ -277,6 +345,12 @@ class Trainer:
     def resume(self, path: Union[str, Path]) -> int:
         """Restore the model, the optimizer, the epoch and the history; returns the epochs completed."""
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        groups = len(ckpt["optimizer_state_dict"]["param_groups"])
+        if groups != len(self.optimizer.param_groups):
+            was, now = groups > 1, self.train_neck
+            raise ValueError(f"{path}: the checkpoint's optimizer holds {groups} parameter group(s) (written with "
+                             f"train_neck={was}) and this trainer {len(self.optimizer.param_groups)} "
+                             f"(train_neck={now}); resume with the train_neck setting of the run that wrote it")
         self.model.load_state_dict(ckpt["model_state_dict"])
         self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
         self.history = {k: list(v) for k, v in ckpt.get("history", {}).items()}

@@ -7,7 +7,8 @@ kpd_roi_features + kpd_roi_targets -> HeatmapHead train step -> checkpoints.
     python scripts/train.py --config configs/default_config.yaml --data_dir data/ \
         --output_dir runs/head [--model best_model.pth|synthetic] [--resume runs/head/checkpoint_epoch_5.pth] \
         [--epochs N] [--batch-size N] [--max-steps N] [--seed S] [--augment] [--precision split|fp32|mixed] [--amp] \
-        [--train heatmap_head|detector] [--coord-weight W] [--coord-temperature T]
+        [--train heatmap_head|detector] [--coord-weight W] [--coord-temperature T] \
+        [--train-neck] [--neck-lr-scale S]
 
 ``--model`` gives the starting weights (a checkpoint, or ``synthetic`` for the
 seeded synthetic state dict; default: the freshly initialised model);
@@ -22,6 +23,12 @@ loss (validation), avg_ADE, pck_*, learning_rate, steps, skipped_steps, seconds.
 decoded keypoints to every step (``Trainer(coord_weight=W)``, DESIGN.md §3k);
 the line then also holds coord_loss and avg_ADE_soft (validation).  It is an
 error with ``--train detector``.
+``--train-neck`` trains the FPN's level-0 path (``backbone.fpn.lateral_convs``
+and ``fpn_convs.0``, which have no pretrained weights) together with the head
+(``Trainer(train_neck=True)``), at ``--neck-lr-scale`` times the
+head's learning rate; the body and ``channel_attention`` stay frozen.  A
+detector trained before such a run must be retrained after it (it reads level
+0 too).  Both are an error with ``--train detector``.
 
 ``--train detector`` trains the person detector instead (``DetectorTrainer``,
 DESIGN.md §3j: kpd_detector_features -> anchor matching + focal / smooth-L1 loss
@@ -74,6 +81,10 @@ def parse_args(argv=None):
                     help="weight of the coordinate term on the soft-argmax decoded keypoints (0: off)")
     ap.add_argument("--coord-temperature", type=float, default=1.0,
                     help="soft-argmax temperature of that term (1.0: the eval forward's decode)")
+    ap.add_argument("--train-neck", action="store_true",
+                    help="also train the FPN's level-0 path under the head (Trainer train_neck=True)")
+    ap.add_argument("--neck-lr-scale", type=float, default=None,
+                    help="learning rate of the neck's parameters relative to the head's (default 1.0)")
     ap.add_argument("--train", default="heatmap_head", choices=["heatmap_head", "detector"],
                     help="what to train on the frozen trunk (default: the heatmap head)")
     ap.add_argument("--device", default="cuda")
@@ -86,6 +97,13 @@ def parse_args(argv=None):
         ap.error("--coord-temperature must be positive and finite")
     if args.train == "detector" and args.coord_weight > 0:
         ap.error("--coord-weight does not apply to --train detector: the detector has no keypoint output")
+    if args.train == "detector" and (args.train_neck or args.neck_lr_scale is not None):
+        ap.error("--train-neck / --neck-lr-scale do not apply to --train detector: the detector's trainer keeps "
+                 "the whole trunk frozen")
+    if args.neck_lr_scale is not None and not args.train_neck:
+        ap.error("--neck-lr-scale needs --train-neck")
+    if args.neck_lr_scale is not None and not (0.0 < args.neck_lr_scale < float("inf")):
+        ap.error("--neck-lr-scale must be positive and finite")
     for name in ("epochs", "batch_size", "max_steps"):
         v = getattr(args, name)
         if v is not None and v < 1:
@@ -139,7 +157,9 @@ def main(argv=None):
         trainer = DetectorTrainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir)
     else:
         trainer = Trainer(model, device, train_dl, val_dl, tcfg, output_dir=args.output_dir, use_amp=args.amp,
-                          coord_weight=args.coord_weight, coord_temperature=args.coord_temperature)
+                          coord_weight=args.coord_weight, coord_temperature=args.coord_temperature,
+                          train_neck=args.train_neck,
+                          neck_lr_scale=1.0 if args.neck_lr_scale is None else args.neck_lr_scale)
     trainer.max_steps = args.max_steps
     if args.resume is not None:
         trainer.resume(args.resume)
