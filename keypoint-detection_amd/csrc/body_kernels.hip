@@ -1505,8 +1505,11 @@ size_t fir_lds_bytes(const FirArgs& a, int K, int S) {
               (size_t)K * K * FIR_CS + (size_t)FIR_CS * a.cout_p + 2 * FIR_CS);
 }
 
+// fir_kernel<K, S> instantiations: features.2 (3x3 s2); features.3 (3x3 s1) only under KPD_FIR_MASK
+static bool fir_has(int K, int S) { return K == 3 && (S == 2 || (KPD_DIAG && S == 1)); }
+
 int fir_pick_rows(FirArgs& a, int K, int S) {
-  if (a.cin_p % 4 || a.Ep % FIR_CS || a.cout_p % 8 || (a.res && (S != 1 || a.cin_p != a.cout_p)) ||
+  if (!fir_has(K, S) || a.cin_p % 4 || a.Ep % FIR_CS || a.cout_p % 8 || (a.res && (S != 1 || a.cin_p != a.cout_p)) ||
       a.cin_p * FIR_CS > 1024 || FIR_CS * a.cout_p > 1024 || K * K * FIR_CS / 4 > 256)
     return 0;
   static const int th_env = kpd_diag_env("KPD_FIR_TH") ? atoi(kpd_diag_env("KPD_FIR_TH")) : 0;   // A/B sweeps
@@ -1522,26 +1525,57 @@ int fir_pick_rows(FirArgs& a, int K, int S) {
 hipError_t launch_fir(const FirArgs& a, int N, int K, int S, hipStream_t st) {
   if (a.TH <= 0 || (a.TH * a.Wo + 1) / 2 * (a.cout_p / 8) > 256) return hipErrorInvalidValue;
   const size_t lds = fir_lds_bytes(a, K, S);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
+  if (lds > 64 * 1024 || !fir_has(K, S)) return hipErrorInvalidValue;
   const dim3 grid((a.Ho + a.TH - 1) / a.TH, N);
-#define FIR(KK, SS) hipLaunchKernelGGL((fir_kernel<KK, SS>), grid, dim3(256), lds, st, a)
-  if (K == 3 && S == 1) FIR(3, 1);
-  else if (K == 3 && S == 2) FIR(3, 2);
-  else if (K == 5 && S == 1) FIR(5, 1);
-  else if (K == 5 && S == 2) FIR(5, 2);
-  else return hipErrorInvalidValue;
-#undef FIR
+  if (S == 2) hipLaunchKernelGGL((fir_kernel<3, 2>), grid, dim3(256), lds, st, a);
+#if KPD_DIAG
+  else hipLaunchKernelGGL((fir_kernel<3, 1>), grid, dim3(256), lds, st, a);
+#endif
   return hipGetLastError();
 }
 
+// ---- exdw / seproj host side: the variant tables, the picks, the launchers ----
+//
+// Every exdw_kernel<K, S, NTC, XT, KC, BL, ACT> instantiation, written once:
+// X(id, K, S, NTC, XT, KC, BL, ACT, path token).  The template arguments are
+// the selection key: CS = 16 NTC, cin_p = 16 KC, XT 4 from 12 output columns
+// up, BL = exdw_bl; ACT_HSWISH serves blocks whose two activations are both
+// hardswish, -1 (the runtime switch) any.  The table is what a forward can
+// reach at image sides 32..1024 and any batch; DESIGN.md ("Body variant
+// tables") records the variants that lost their measurement.
+#define EXDW_VARIANTS(X)                                                                                \
+  X(K3S1_C16_XT4, 3, 1, 1, 4, 2, false, -1, KP_EXDW_RT_K3S1C16_XT4) /* features.3, fir23 declined */    \
+  X(K5S2_C16_XT4, 5, 2, 1, 4, 2, false, ACT_HSWISH, KP_EXDW_HS_S2C16) /* features.4 */                  \
+  X(K5S2_C16_XT2, 5, 2, 1, 2, 2, false, -1, KP_EXDW_RT_K5S2C16_XT2)                                     \
+  X(K5S1_C16_XT4, 5, 1, 1, 4, 3, false, ACT_HSWISH, KP_EXDW_HS_S1C16) /* features.5-8 */                \
+  X(K5S1_C16_XT2, 5, 1, 1, 2, 3, false, -1, KP_EXDW_RT_K5S1C16_XT2)                                     \
+  X(K5S2_C32_XT4, 5, 2, 2, 4, 3, false, -1, KP_EXDW_RT_K5S2C32_XT4) /* features.9 */                    \
+  X(K5S2_C32_XT2, 5, 2, 2, 2, 3, false, ACT_HSWISH, KP_EXDW_HS_S2C32)                                   \
+  X(BL_XT4, 5, 1, 2, 4, 6, true, ACT_HSWISH, KP_EXDW_BL_XT4) /* features.10 / 11 before seproj */       \
+  X(BL_XT2, 5, 1, 2, 2, 6, true, ACT_HSWISH, KP_EXDW_BL_XT2)                                            \
+  X(K5S1_C32_XT4, 5, 1, 2, 4, 6, false, -1, KP_EXDW_RT_K5S1C32_XT4) /* ... before se_kernel */          \
+  X(K5S1_C32_XT2, 5, 1, 2, 2, 6, false, -1, KP_EXDW_RT_K5S1C32_XT2)
+#if KPD_DIAG   // features.3 under 12 columns: fir23 takes every such map unless KPD_NO_FIR23 turns it off
+#define EXDW_DIAG_VARIANTS(X) X(K3S1_C16_XT2, 3, 1, 1, 2, 2, false, -1, KP_EXDW_RT_K3S1C16_XT2)
+#else
+#define EXDW_DIAG_VARIANTS(X)
+#endif
+#define EXDW_ALL_VARIANTS(X) EXDW_VARIANTS(X) EXDW_DIAG_VARIANTS(X)
+
+enum ExDwVariant {
+#define X(id, ...) EXDW_##id,
+  EXDW_ALL_VARIANTS(X)
+#undef X
+};
+
 // the BL variant of exdw_kernel: the 576-wide stride-1 SE blocks (32-channel
 // slices of a 96-channel input; KPD_EXDW_NOBL=1, diagnostic build: off)
-bool exdw_bl(const ExDwArgs& a, int K) {
+static bool exdw_bl(const ExDwArgs& a, int K) {
   static const bool off = kpd_diag_env("KPD_EXDW_NOBL") != nullptr;
   return !off && K == 5 && a.Hi == a.Ho && a.CS == 32 && a.cin_p == 96 && a.pooled && a.part && a.nband <= 1;
 }
 
-size_t exdw_lds_bytes(const ExDwArgs& a, int K) {
+static size_t exdw_lds_bytes(const ExDwArgs& a, int K) {
   // a band's input rows: at most ceil(Ho / nband) output rows' worth
   const int nb = a.nband > 1 ? a.nband : 1, S = a.Hi > a.Ho ? 2 : 1;
   const int Pin = std::min(a.Hi, ((a.Ho + nb - 1) / nb - 1) * S + K) * a.Wi, Po = a.Ho * a.Wo;
@@ -1552,140 +1586,101 @@ size_t exdw_lds_bytes(const ExDwArgs& a, int K) {
   return 4 * main;
 }
 
+// Which instantiation a block takes (pure host code, no HIP call), or -1: no
+// variant, or the slice does not fit the LDS.  Every key has one row.
+int exdw_pick(const ExDwArgs& a, int K, int S) {
+  if (a.CS <= 0 || a.cin_p % 16 || exdw_lds_bytes(a, K) > 160 * 1024) return -1;
+  const int kc = a.cin_p / 16, xt = a.Wo >= 12 ? 4 : 2;
+  const bool bl = exdw_bl(a, K), hs = a.act_e == ACT_HSWISH && a.act_d == ACT_HSWISH;
+#define X(id, K_, S_, NTC, XT, KC, BL, ACT, tok)                                                          \
+  if (K == K_ && S == S_ && a.CS == 16 * NTC && xt == XT && kc == KC && bl == BL && (ACT < 0 || hs))      \
+    return EXDW_##id;
+  EXDW_ALL_VARIANTS(X)
+#undef X
+  return -1;
+}
+
 hipError_t launch_exdw(const ExDwArgs& a, int N, int K, int S, hipStream_t st) {
-  const int kc = a.cin_p / 16;
-  if ((a.CS != 16 && a.CS != 32 && a.CS != 48) || a.Ep % a.CS || a.cin_p % 16 || (kc != 2 && kc != 3 && kc != 6) ||
-      !a.we ||
+  if ((a.CS != 16 && a.CS != 32) || a.Ep % a.CS || a.cin_p % 16 || !a.we ||
       (a.part && (!a.pooled || !a.w1 || a.sq <= 0 || a.sq > 144 || a.C % 4)) ||
       (a.nband > 1 && (a.pooled || a.part || a.nband > a.Ho)))
     return hipErrorInvalidValue;
+  const int v = exdw_pick(a, K, S);
+  if (v < 0) return hipErrorInvalidValue;
   const size_t lds = exdw_lds_bytes(a, K);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   const dim3 grid(a.Ep / a.CS, N, a.nband > 1 ? a.nband : 1);
-  const bool xt4 = a.Wo >= 12;
-  // the coarse SE blocks (features.4..11) use hardswish for both: that
-  // instance compiled with the constant (KPD_EXDW_RTACT=1, diagnostic build: the runtime switch)
-  static const bool rtact = kpd_diag_env("KPD_EXDW_RTACT") != nullptr;
-  const bool hs = !rtact && a.act_e == ACT_HSWISH && a.act_d == ACT_HSWISH;
-  if (exdw_bl(a, K)) {
-    kpd_path(xt4 ? KP_EXDW_BL_XT4 : KP_EXDW_BL_XT2);
-    if (hs && xt4) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 4, 6, true, ACT_HSWISH>), grid, dim3(256), lds, st, a);
-    else if (hs) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 2, 6, true, ACT_HSWISH>), grid, dim3(256), lds, st, a);
-    else if (xt4) hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 4, 6, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((exdw_kernel<5, 1, 2, 2, 6, true>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
+  switch (v) {
+#define X(id, K_, S_, NTC, XT, KC, BL, ACT, tok) \
+  case EXDW_##id: kpd_path(tok); hipLaunchKernelGGL((exdw_kernel<K_, S_, NTC, XT, KC, BL, ACT>), grid, dim3(256), lds, st, a); break;
+    EXDW_ALL_VARIANTS(X)
+#undef X
   }
-  // the hardswish instances the model's blocks take: features.4 (5x5 s2, 16-channel slices of 32
-  // input channels), .5-.8 (5x5 s1, 16-channel slices, 48 input channels), .9 (5x5 s2, 32-channel slices)
-  if (hs && K == 5 && S == 2 && a.CS == 16 && kc == 2 && xt4) {
-    kpd_path(KP_EXDW_HS_S2C16);
-    hipLaunchKernelGGL((exdw_kernel<5, 2, 1, 4, 2, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-  }
-  if (hs && K == 5 && S == 1 && a.CS == 16 && kc == 3 && xt4) {
-    kpd_path(KP_EXDW_HS_S1C16);
-    hipLaunchKernelGGL((exdw_kernel<5, 1, 1, 4, 3, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-  }
-  if (hs && K == 5 && S == 2 && a.CS == 32 && kc == 3 && !xt4) {
-    kpd_path(KP_EXDW_HS_S2C32);
-    hipLaunchKernelGGL((exdw_kernel<5, 2, 2, 2, 3, false, ACT_HSWISH>), grid, dim3(256), lds, st, a);
-    return hipGetLastError();
-  }
-#define EXDW_KC(KK, SS, NTC, XT)                                                                        \
-  do {                                                                                                  \
-    if (kc == 2) hipLaunchKernelGGL((exdw_kernel<KK, SS, NTC, XT, 2>), grid, dim3(256), lds, st, a);   \
-    else if (kc == 3) hipLaunchKernelGGL((exdw_kernel<KK, SS, NTC, XT, 3>), grid, dim3(256), lds, st, a); \
-    else hipLaunchKernelGGL((exdw_kernel<KK, SS, NTC, XT, 6>), grid, dim3(256), lds, st, a);           \
-  } while (0)
-#define EXDW(KK, SS)                                    \
-  do {                                                  \
-    if (a.CS == 16) {                                   \
-      if (xt4) EXDW_KC(KK, SS, 1, 4);                   \
-      else EXDW_KC(KK, SS, 1, 2);                       \
-    } else if (a.CS == 32) {                            \
-      if (xt4) EXDW_KC(KK, SS, 2, 4);                   \
-      else EXDW_KC(KK, SS, 2, 2);                       \
-    } else {                                            \
-      EXDW_KC(KK, SS, 3, 2);                            \
-    }                                                   \
-  } while (0)
-  kpd_path(a.CS != 48 && xt4 ? KP_EXDW_RT_XT4 : KP_EXDW_RT_XT2);
-  if (K == 3 && S == 1) EXDW(3, 1);
-  else if (K == 5 && S == 1) EXDW(5, 1);
-  else if (K == 5 && S == 2) EXDW(5, 2);
-  else return hipErrorInvalidValue;
-#undef EXDW
-#undef EXDW_KC
   return hipGetLastError();
 }
 
-size_t seproj_lds_bytes(const SeProjArgs& a) {
-  const int mt = (a.Po + 15) / 16;
+// Every seproj_kernel<MT, NTT, NWV> instantiation: X(id, row tiles per
+// workgroup, 16-column tiles, waves, path token)
+#define SEPROJ_VARIANTS(X)          \
+  X(M3T1, 3, 1, 8, KP_SEPROJ_M3T1)  \
+  X(M3T2, 3, 2, 8, KP_SEPROJ_M3T2)  \
+  X(M3T3, 3, 3, 8, KP_SEPROJ_M3T3)
+
+enum SeProjVariant {
+#define X(id, ...) SEPROJ_##id,
+  SEPROJ_VARIANTS(X)
+#undef X
+};
+
+// The variant and launch geometry of a project (pure host code, no HIP call);
+// v = -1: no variant, or over the LDS
+SeProjPick seproj_pick(const SeProjArgs& a, int N) {
+  SeProjPick k{-1};
+  if (a.NT <= 0 || a.NT % 16 || a.cout_p % a.NT || a.C < 4) return k;
+  const int mt_all = (a.Po + 15) / 16;
+  // the 192-pixel maps split their rows over workgroups, each recomputing the
+  // excitation: with 48-column tiles (all of features.4..8's outputs) four
+  // groups of 48 rows (256 workgroups at 64 images, 4 excitations per image)
+  k.msplit = mt_all == 12 ? (a.NT >= 48 ? 4 : 2) : 1;
+  k.mt = (mt_all + k.msplit - 1) / k.msplit;
+  // three row tiles per workgroup: eight waves split the project's K chunks
+  // (one wave per SIMD at four leaves the fp32-MFMA K loop exposed): 12.1 ->
+  // 9.6 us per launch on the 48-pixel maps
+  k.waves = k.mt == 3 ? 8 : 4;
   const size_t nq4 = a.C / 4, ngrp = std::max<size_t>(1, std::min<size_t>(16, 256 / nq4));
-  const size_t red = std::max({(size_t)4 * mt * 16 * a.NT, (size_t)a.nsl * a.sq, ngrp * a.C});
-  return 4 * ((size_t)a.Ep + 256 + red);
+  k.lds = 4 * ((size_t)a.Ep + 256 + std::max({(size_t)k.waves * k.mt * 16 * a.NT, (size_t)a.nsl * a.sq, ngrp * a.C}));
+  k.grid = dim3(a.cout_p / a.NT, N, k.msplit);
+  if (k.lds > 160 * 1024) return k;
+#define X(id, MT, NTT, NWV, tok) \
+  if (k.mt == MT && a.NT == 16 * NTT && k.waves == NWV) k.v = SEPROJ_##id;
+  SEPROJ_VARIANTS(X)
+#undef X
+  return k;
 }
 
 hipError_t launch_seproj(const SeProjArgs& a, int N, hipStream_t st) {
-  const int mt_all = (a.Po + 15) / 16;
   if (a.Ep % 16 || a.NT % 16 || a.cout_p % a.NT || a.sq > 144 || a.C > a.Ep || a.C % 4 ||
       (size_t)a.nsl * a.sq > 6 * 256 * 4 || (a.nsl * a.sq) % 4)
     return hipErrorInvalidValue;
-  // the 192-pixel maps split their rows over workgroups, each recomputing the
-  // excitation: with 48-column tiles (all of features.4..8's outputs) four
-  // groups of 48 rows (256 workgroups at 64 images, 4 excitations per image),
-  // with 16-column tiles two (384 workgroups, 6 excitations per image)
-  static const int msplit_env = kpd_diag_env("KPD_SEPROJ_MSPLIT") ? atoi(kpd_diag_env("KPD_SEPROJ_MSPLIT")) : 0;
-  const int msplit = mt_all == 12 ? (msplit_env > 0 ? msplit_env : (a.NT >= 48 ? 4 : 2)) : 1;
-  const int mt = (mt_all + msplit - 1) / msplit;
-  SeProjArgs b = a;
-  // the 48-pixel maps (3 row tiles): eight waves split the project's K
-  // chunks (one wave per SIMD at four leaves the fp32-MFMA K loop exposed):
-  // 12.1 -> 9.6 us per launch.  The 192-pixel maps (6 row tiles per
-  // workgroup) measured 13.5 -> 16.9 us with eight, so they keep four.
-  // KPD_SEPROJ_NWV = 4 / 8 forces one (A/B).
-  static const int nwv_env = kpd_diag_env("KPD_SEPROJ_NWV") ? atoi(kpd_diag_env("KPD_SEPROJ_NWV")) : 0;
-  const int nwv = nwv_env == 4 || nwv_env == 8 ? nwv_env : (mt == 3 ? 8 : 4);
-  const size_t lds_m = 4 * ((size_t)a.Ep + 256 + std::max({(size_t)nwv * mt * 16 * a.NT, (size_t)a.nsl * a.sq,
-                                                             std::max<size_t>(1, std::min<size_t>(16, 256 / (a.C / 4))) * a.C}));
-  if (lds_m > 160 * 1024) return hipErrorInvalidValue;
-  const dim3 grid(a.cout_p / a.NT, N, msplit);
-  const int ntt = a.NT / 16;
-#define SEP(M, T)                                                                                   \
-  do {                                                                                              \
-    if (nwv == 8) hipLaunchKernelGGL((seproj_kernel<M, T, 8>), grid, dim3(512), lds_m, st, b);     \
-    else hipLaunchKernelGGL((seproj_kernel<M, T, 4>), grid, dim3(256), lds_m, st, b);              \
-  } while (0)
-  if (mt == 3 && ntt == 1) kpd_path(KP_SEPROJ_M3T1, nwv);
-  else if (mt == 3 && ntt == 2) kpd_path(KP_SEPROJ_M3T2, nwv);
-  else if (mt == 3 && ntt == 3) kpd_path(KP_SEPROJ_M3T3, nwv);
-  else if (mt == 6 && ntt == 1) kpd_path(KP_SEPROJ_M6T1, nwv);
-  else if (mt == 4 && ntt == 1) kpd_path(KP_SEPROJ_M4T1, nwv);
-  else if (mt == 12 && ntt == 1) kpd_path(KP_SEPROJ_M12T1, nwv);
-  else if (mt == 12 && ntt == 3) kpd_path(KP_SEPROJ_M12T3, nwv);
-  if (mt == 3 && ntt == 1) SEP(3, 1);
-  else if (mt == 3 && ntt == 2) SEP(3, 2);
-  else if (mt == 3 && ntt == 3) SEP(3, 3);
-  else if (mt == 6 && ntt == 1) SEP(6, 1);
-  else if (mt == 4 && ntt == 1) SEP(4, 1);
-  else if (mt == 12 && ntt == 1) SEP(12, 1);
-  else if (mt == 12 && ntt == 3) SEP(12, 3);
-  else return hipErrorInvalidValue;
-#undef SEP
+  const SeProjPick k = seproj_pick(a, N);
+  switch (k.v) {
+#define X(id, MT, NTT, NWV, tok) \
+  case SEPROJ_##id: kpd_path(tok); hipLaunchKernelGGL((seproj_kernel<MT, NTT, NWV>), k.grid, dim3(NWV * 64), k.lds, st, a); break;
+    SEPROJ_VARIANTS(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
+// features.1 of mobilenet_v3_small: 3x3 stride 2 + ReLU, the one block without an expand
+bool dwsum_has(int k, int s, int act) { return k == 3 && s == 2 && act == ACT_RELU; }
+
 hipError_t launch_dwsum(const float* in, int N, int Hi, int Wi, const float* w, const float* b, int act, float* out,
                          int Ho, int Wo, int k, int s, float* part, int* ntiles, hipStream_t st) {
-  if (kDwsTH * ((Wo + 3) / 4) * 4 > 256) return hipErrorInvalidValue;
+  if (kDwsTH * ((Wo + 3) / 4) * 4 > 256 || !dwsum_has(k, s, act)) return hipErrorInvalidValue;
   const dim3 grid((Ho + kDwsTH - 1) / kDwsTH, N);
   *ntiles = (int)grid.x;
-  if (k == 3 && s == 2 && act == ACT_RELU)   // features.1 of mobilenet_v3_small
-    hipLaunchKernelGGL((dwsum_kernel<3, 2, ACT_RELU>), grid, dim3(256), 0, st, in, Hi, Wi, w, b, act, out, Ho, Wo, part);
-  else if (k == 3 && s == 2) hipLaunchKernelGGL((dwsum_kernel<3, 2>), grid, dim3(256), 0, st, in, Hi, Wi, w, b, act, out, Ho, Wo, part);
-  else if (k == 3 && s == 1) hipLaunchKernelGGL((dwsum_kernel<3, 1>), grid, dim3(256), 0, st, in, Hi, Wi, w, b, act, out, Ho, Wo, part);
-  else return hipErrorInvalidValue;
+  hipLaunchKernelGGL((dwsum_kernel<3, 2, ACT_RELU>), grid, dim3(256), 0, st, in, Hi, Wi, w, b, act, out, Ho, Wo, part);
   return hipGetLastError();
 }
 

@@ -259,7 +259,9 @@ struct ExDwArgs {
   unsigned long long* stamps;   // diagnostic phase stamps, [grid][8] (KPD_STAMPS), normally null
   int nband;             // > 1 (no SE only): output rows split over nband workgroups per (image, slice)
 };
-size_t exdw_lds_bytes(const ExDwArgs& a, int K);
+// which exdw_kernel instantiation (body_kernels.hip, EXDW_VARIANTS) a block of
+// kernel size K, stride S takes; -1: none, or over the LDS -- not eligible
+int exdw_pick(const ExDwArgs& a, int K, int S);
 hipError_t launch_exdw(const ExDwArgs& a, int N, int K, int S, hipStream_t st);
 // SE excitation (from exdw_kernel's fc1 partials) + project 1x1 + residual
 // (body_kernels.hip, seproj_kernel)
@@ -276,10 +278,18 @@ struct SeProjArgs {
   unsigned long long* stamps;   // diagnostic phase stamps, [grid][8] (KPD_STAMPS), normally null
   const float* sesc;     // optional precomputed excitation [N][Ep] (se_excite_kernel); null: computed here
 };
-size_t seproj_lds_bytes(const SeProjArgs& a);
+// the seproj_kernel instantiation (SEPROJ_VARIANTS; -1: none) of a project on
+// N images and its launch geometry: row groups, row tiles per workgroup, waves
+struct SeProjPick {
+  int v, msplit, mt, waves;
+  dim3 grid;
+  size_t lds;
+};
+SeProjPick seproj_pick(const SeProjArgs& a, int N);
 hipError_t launch_seproj(const SeProjArgs& a, int N, hipStream_t st);
 // features.1 (16 channels, no expand): depthwise + per-tile channel sums, then
 // excitation + project (body_kernels.hip, dwsum_kernel / se16_proj_kernel)
+bool dwsum_has(int k, int s, int act);   // the depthwise dwsum_kernel is compiled for
 hipError_t launch_dwsum(const float* in, int N, int Hi, int Wi, const float* w, const float* b, int act, float* out,
                          int Ho, int Wo, int k, int s, float* part, int* ntiles, hipStream_t st);
 hipError_t launch_se16_proj(const float* d, int N, int npx, int ntiles, const float* part, const float* w1,
@@ -423,22 +433,23 @@ enum : unsigned {
   X(KP_GENERIC_SE, "generic+se_kernel", KP_BLOCK)                                                  \
   X(KP_GENERIC, "generic", KP_BLOCK)                                                               \
   X(KP_SE_EXCITE, "se_excite", KP_BLOCK)                                                           \
-  /* launch_exdw */                                                                                \
+  /* launch_exdw (EXDW_VARIANTS): activation hs = compile-time hardswish, rt = runtime switch */   \
   X(KP_EXDW_BL_XT4, "exdw:bl:xt4", KP_BLOCK)                                                       \
   X(KP_EXDW_BL_XT2, "exdw:bl:xt2", KP_BLOCK)                                                       \
   X(KP_EXDW_HS_S2C16, "exdw:hs:k5s2:cs16:xt4", KP_BLOCK)                                           \
   X(KP_EXDW_HS_S1C16, "exdw:hs:k5s1:cs16:xt4", KP_BLOCK)                                           \
   X(KP_EXDW_HS_S2C32, "exdw:hs:k5s2:cs32:xt2", KP_BLOCK)                                           \
-  X(KP_EXDW_RT_XT4, "exdw:rt:xt4", KP_BLOCK)                                                       \
-  X(KP_EXDW_RT_XT2, "exdw:rt:xt2", KP_BLOCK)                                                       \
-  /* launch_seproj: row tiles per workgroup, 16-column tiles, waves */                             \
-  X(KP_SEPROJ_M3T1, "seproj:m3:t1:w%d", KP_BLOCK)                                                  \
-  X(KP_SEPROJ_M3T2, "seproj:m3:t2:w%d", KP_BLOCK)                                                  \
-  X(KP_SEPROJ_M3T3, "seproj:m3:t3:w%d", KP_BLOCK)                                                  \
-  X(KP_SEPROJ_M6T1, "seproj:m6:t1:w%d", KP_BLOCK | KP_DIAG)                                        \
-  X(KP_SEPROJ_M4T1, "seproj:m4:t1:w%d", KP_BLOCK | KP_DIAG)                                        \
-  X(KP_SEPROJ_M12T1, "seproj:m12:t1:w%d", KP_BLOCK | KP_DIAG)                                      \
-  X(KP_SEPROJ_M12T3, "seproj:m12:t3:w%d", KP_BLOCK | KP_DIAG)                                      \
+  X(KP_EXDW_RT_K3S1C16_XT4, "exdw:rt:k3s1:cs16:xt4", KP_BLOCK)                                     \
+  X(KP_EXDW_RT_K3S1C16_XT2, "exdw:rt:k3s1:cs16:xt2", KP_BLOCK | KP_DIAG)                           \
+  X(KP_EXDW_RT_K5S2C16_XT2, "exdw:rt:k5s2:cs16:xt2", KP_BLOCK)                                     \
+  X(KP_EXDW_RT_K5S1C16_XT2, "exdw:rt:k5s1:cs16:xt2", KP_BLOCK)                                     \
+  X(KP_EXDW_RT_K5S2C32_XT4, "exdw:rt:k5s2:cs32:xt4", KP_BLOCK)                                     \
+  X(KP_EXDW_RT_K5S1C32_XT4, "exdw:rt:k5s1:cs32:xt4", KP_BLOCK)                                     \
+  X(KP_EXDW_RT_K5S1C32_XT2, "exdw:rt:k5s1:cs32:xt2", KP_BLOCK)                                     \
+  /* launch_seproj (SEPROJ_VARIANTS): row tiles per workgroup, 16-column tiles, waves */           \
+  X(KP_SEPROJ_M3T1, "seproj:m3:t1:w8", KP_BLOCK)                                                   \
+  X(KP_SEPROJ_M3T2, "seproj:m3:t2:w8", KP_BLOCK)                                                   \
+  X(KP_SEPROJ_M3T3, "seproj:m3:t3:w8", KP_BLOCK)                                                   \
   /* conv() / launch_conv / launch_pw_small */                                                     \
   X(KP_CONV_PW_SMALL, "conv:pw_small", KP_BLOCK | KP_LAST | KP_LAT)                                \
   X(KP_CONV_K3, "conv:k3", KP_FPN0 | KP_HM | KP_KH)                                                \

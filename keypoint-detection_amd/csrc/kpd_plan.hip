@@ -693,8 +693,8 @@ static int block_dwsum(Pass& ps, const Blk& b) {
   const int B = ps.d.B, i = b.i, ho = b.ho, wo = b.wo;
   static const bool no_f1 = kpd_diag_env("KPD_NO_F1") != nullptr;   // A/B switch
   if (!(!no_f1 && !bn.has_exp && bn.cfg.se && bn.dw.Cp == 16 && bn.cfg.cout == 16 && bn.project.cout_p == 16 &&
-        bn.project.cin_p == 16 && bn.project.k == 1 && !bn.project.bf16 && bn.se.sq <= 16 && bn.dw.k == 3 &&
-        !(bn.cfg.s == 1 && bn.cfg.cin == bn.cfg.cout) && 4 * ((wo + 3) / 4) * 4 <= 256))
+        bn.project.cin_p == 16 && bn.project.k == 1 && !bn.project.bf16 && bn.se.sq <= 16 &&
+        dwsum_has(bn.dw.k, bn.dw.s, bn.dw.act) && 4 * ((wo + 3) / 4) * 4 <= 256))
     return 0;
   int nt = 0;
   kpd_path(KP_F1_DWSUM);
@@ -764,8 +764,9 @@ static int block_fir(Pass& ps, const Blk& b) {
 }
 
 // coarse maps: expand + depthwise (+ SE means) fused when the image fits LDS.
-// Fills exdw_kernel's arguments; false: the block does not take the fused kernel
-static bool exdw_fill(const Pass& ps, const Blk& b, ExDwArgs& xa) {
+// Fills exdw_kernel's arguments (part: with the SE fc1 partials seproj_kernel
+// reads); false: the block does not take the fused kernel
+static bool exdw_fill(const Pass& ps, const Blk& b, ExDwArgs& xa, bool part = false) {
   const DevBneck& bn = b.bn; const Work& w = *ps.w;
   const int B = ps.d.B, i = b.i;
   xa.x = b.x; xa.Hi = b.hi; xa.Wi = b.wi; xa.cin_p = b.inp;
@@ -773,21 +774,19 @@ static bool exdw_fill(const Pass& ps, const Blk& b, ExDwArgs& xa) {
   xa.be = bn.has_exp ? bn.expand.b : nullptr;
   xa.act_e = bn.cfg.act; xa.wd = bn.dw.w; xa.bd = bn.dw.b; xa.act_d = bn.dw.act; xa.Ep = bn.dw.Cp;
   xa.out = w.d[i]; xa.Ho = b.ho; xa.Wo = b.wo; xa.pooled = bn.cfg.se ? w.pool : nullptr;
-  if (!(!no_fuse() && b.hi * b.wi <= kFuseMaxPix && bn.has_exp && bn.expand.cout_p == bn.dw.Cp && b.inp % 16 == 0 &&
-        b.inp <= 96))
+  if (part) { xa.part = w.separt; xa.w1 = bn.se.w1; xa.sq = bn.se.sq; xa.C = bn.se.C; }
+  if (!(!no_fuse() && b.hi * b.wi <= kFuseMaxPix && bn.has_exp && bn.expand.cout_p == bn.dw.Cp && b.inp <= 96))
     return false;
   // slice width fixed per layer (never per batch: the fc1 partial sums
-  // must not depend on what an image is batched with)
-  static const int cs_env = kpd_diag_env("KPD_EXDW_CS") ? atoi(kpd_diag_env("KPD_EXDW_CS")) : 0;   // A/B sweeps
-  // 32 channels from 288 expanded channels up, else 16 (48 for the
-  // 576-wide blocks measured slower: 188 VGPRs, 30 vs 23 us)
-  xa.CS = cs_env > 0 ? cs_env : (bn.dw.Cp >= 288 ? 32 : 16);
+  // must not depend on what an image is batched with): 32 channels from 288
+  // expanded channels up, else 16
+  xa.CS = bn.dw.Cp >= 288 ? 32 : 16;
   // no SE and under two workgroups per CU: split the output rows in two
   // bands (features.3 at 64 images: 384 -> 768 workgroups)
   static const int nband_env = kpd_diag_env("KPD_EXDW_NBAND") ? atoi(kpd_diag_env("KPD_EXDW_NBAND")) : 0;   // A/B
   xa.nband = !bn.cfg.se && (long)(bn.dw.Cp / xa.CS) * B < 512 ? 2 : 1;
   if (nband_env > 0 && !bn.cfg.se) xa.nband = std::min(nband_env, b.ho);
-  return bn.dw.Cp % xa.CS == 0 && exdw_lds_bytes(xa, bn.dw.k) <= 160 * 1024;
+  return bn.dw.Cp % xa.CS == 0 && exdw_pick(xa, bn.dw.k, bn.dw.s) >= 0;
 }
 
 static int launch_exdw_block(Pass& ps, const Blk& b, ExDwArgs& xa) {
@@ -803,28 +802,27 @@ static int launch_exdw_block(Pass& ps, const Blk& b, ExDwArgs& xa) {
 static int block_exdw_seproj(Pass& ps, const Blk& b) {
   const DevBneck& bn = b.bn; Work& w = *ps.w;
   const int B = ps.d.B, i = b.i, ho = b.ho, wo = b.wo;
-  ExDwArgs xa{};
-  const bool fused = exdw_fill(ps, b, xa);
   static const bool no_seproj = kpd_diag_env("KPD_NO_SEPROJ") != nullptr;   // A/B switch
-  const bool seproj = fused && bn.cfg.se && !no_seproj && bn.project.k == 1 && !bn.project.bf16 &&
-                      bn.project.cin_p == bn.dw.Cp && bn.se.sq <= 144 && bn.se.C % 4 == 0 &&
-                      (ho * wo == 48 || ho * wo == 192) && (size_t)(bn.dw.Cp / xa.CS) * bn.se.sq <= kSePartFloats;
-  if (!seproj) return 0;
-  xa.part = w.separt; xa.w1 = bn.se.w1; xa.sq = bn.se.sq; xa.C = bn.se.C;
-  kpd_path(ho * wo == 48 ? KP_EXDW_SEPROJ48 : KP_EXDW_SEPROJ192);
-  if (int rc = launch_exdw_block(ps, b, xa)) return rc;
+  if (!(bn.cfg.se && !no_seproj && bn.project.k == 1 && !bn.project.bf16 && bn.project.cin_p == bn.dw.Cp &&
+        bn.se.sq <= 144 && bn.se.C % 4 == 0 && (ho * wo == 48 || ho * wo == 192)))
+    return 0;
+  ExDwArgs xa{};
+  if (!exdw_fill(ps, b, xa, true) || (size_t)(bn.dw.Cp / xa.CS) * bn.se.sq > kSePartFloats) return 0;
   SeProjArgs sa{};
   sa.d = w.d[i]; sa.Po = ho * wo; sa.Ep = bn.dw.Cp;
   sa.part = w.separt; sa.nsl = bn.dw.Cp / xa.CS; sa.sq = bn.se.sq; sa.C = bn.se.C;
   sa.b1 = bn.se.b1; sa.w2t = bn.se.w2; sa.b2 = bn.se.b2;
   sa.wp = static_cast<const float*>(bn.project.w); sa.bp = bn.project.b; sa.cout_p = bn.project.cout_p;
-  static const int nt_env = kpd_diag_env("KPD_SEPROJ_NT") ? atoi(kpd_diag_env("KPD_SEPROJ_NT")) : 0;
   // 192-pixel maps: all 48 output channels per workgroup and the rows in
-  // four (launch_seproj), so an image's excitation is recomputed by 4
+  // four (seproj_pick), so an image's excitation is recomputed by 4
   // workgroups instead of 6 (its fc2 weight columns are most of a
   // workgroup's L2 reads): body -8..-12 us at C2 (same-box A/B)
-  sa.NT = nt_env > 0 ? nt_env : (sa.Po == 48 ? 32 : 48);
+  sa.NT = sa.Po == 48 ? 32 : 48;
   if (sa.cout_p % sa.NT) sa.NT = 16;
+  const SeProjPick pick = seproj_pick(sa, B);
+  if (pick.v < 0) return 0;
+  kpd_path(ho * wo == 48 ? KP_EXDW_SEPROJ48 : KP_EXDW_SEPROJ192);
+  if (int rc = launch_exdw_block(ps, b, xa)) return rc;
   const bool res = bn.cfg.s == 1 && bn.cfg.cin == bn.cfg.cout;
   sa.res = res ? b.x : nullptr;
   sa.out = w.o[i];
@@ -836,7 +834,7 @@ static int block_exdw_seproj(Pass& ps, const Blk& b) {
     HIP_TRY(launch_se_excite(sa, B, w.sesc[i], ps.st));
     sa.sesc = w.sesc[i];
   }
-  sa.stamps = ps.take_stamps("stamps_seproj_" + std::to_string(i), (size_t)(sa.cout_p / sa.NT) * B * 2);   // (x msplit)
+  sa.stamps = ps.take_stamps("stamps_seproj_" + std::to_string(i), (size_t)pick.grid.x * pick.grid.y * pick.grid.z);
   HIP_TRY(launch_seproj(sa, B, ps.st));
   return 1;
 }

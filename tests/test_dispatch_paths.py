@@ -42,19 +42,26 @@ TAP_LEVEL = (0, 3, 8, 11)
 # "precision>token" holds in that precision only
 CASES = {
     # seproj at 48 pixels on features.4-8 (no se_excite: C < 288), the 12-pixel
-    # blocks fused without seproj, the small + reuse lateral chain, fpn0x tpc 1
+    # blocks fused without seproj, the small + reuse lateral chain, fpn0x tpc 1;
+    # output maps under 12 columns: the two-column exdw kernels of every block
     "128x96": (128, 96, 2, ("split",),
                ["f1:dwsum+se16_proj", "f4:exdw+seproj:po48", "f5:exdw+seproj:po48", "f6:exdw+seproj:po48",
                 "f7:exdw+seproj:po48", "f8:exdw+seproj:po48", "f4:seproj:m3:t1:w8",
+                "f4:exdw:rt:k5s2:cs16:xt2", "f5:exdw:rt:k5s1:cs16:xt2", "f8:exdw:rt:k5s1:cs16:xt2",
+                "f9:exdw:hs:k5s2:cs32:xt2", "f10:exdw:rt:k5s1:cs32:xt2", "f11:exdw:rt:k5s1:cs32:xt2",
                 "f9:exdw+se_kernel+project", "f10:exdw+se_kernel+project", "f11:exdw+se_kernel+project",
                 "lateral:chain", "lateral_chain:split:small+reuse", "level0:fpn0x:tpc1"],
                ["f4:se_excite", "f8:se_excite", "lat0:lateral_stream"]),
     # level 0 (125 x 95) is not 4x lateral 1 (32 x 24): lateral_stream with
     # non-integer nearest indexing, the fp32 level-0 conv, separate channel
-    # statistics -- in split and mixed precision too; seproj po192 as at 256 x 192
+    # statistics -- in split and mixed precision too; seproj po192 as at 256 x 192:
+    # 16 x 12 outputs on the four-column hardswish exdw kernels, features.10 / 11
+    # (4 x 3, with fc1 partials) on the two-column BL kernel
     "250x190": (250, 190, 2, ("fp32", "split", "mixed"),
                 ["lat0:lateral_stream", "level0:conv", "fpn0:conv:k3", "topk:channel_stats",
                  "f4:exdw+seproj:po192", "f8:exdw+seproj:po192", "f4:seproj:m3:t3:w8",
+                 "f4:exdw:hs:k5s2:cs16:xt4", "f5:exdw:hs:k5s1:cs16:xt4", "f8:exdw:hs:k5s1:cs16:xt4",
+                 "f10:exdw:bl:xt2", "f11:exdw:bl:xt2",
                  "f9:exdw+seproj:po48", "f9:se_excite", "f9:seproj:m3:t2:w8", "lateral:chain",
                  "lateral_chain:fp32:small"],
                 ["level0:fpn0x:tpc*", "level0:conv+stats", "lat0:split_rows"]),
@@ -80,13 +87,14 @@ CASES = {
                 ["f5:exdw+seproj:po192", "f9:exdw+seproj:po48"]),
     # features.5-8 fused at exactly kFuseMaxPix = 768 pixels, seproj po192 +
     # se_excite (+ exdw_bl) on the 576-wide blocks, features.1 generic, lateral 3
-    # of 192 pixels: per-level lateral convs + split_rows, fpn0x tpc 12
+    # of 192 pixels: per-level lateral convs + split_rows, fpn0x tpc 12;
+    # features.9 writes 12 columns: its four-column (runtime-activation) exdw kernel
     "512x384": (512, 384, 1, ("split",),
                 ["f1:generic+se_kernel", "f4:generic+se_kernel", "f5:exdw+se_kernel+project",
                  "f8:exdw+se_kernel+project", "f9:exdw+seproj:po192", "f10:exdw+seproj:po192",
                  "f11:exdw+seproj:po192", "f9:se_excite", "f10:se_excite", "f11:se_excite",
-                 "f10:exdw:bl:xt4", "f11:exdw:bl:xt4", "lateral:per_level", "lat0:split_rows", "lat1:split_rows",
-                 "level0:fpn0x:tpc12"],
+                 "f9:exdw:rt:k5s2:cs32:xt4", "f10:exdw:bl:xt4", "f11:exdw:bl:xt4", "lateral:per_level",
+                 "lat0:split_rows", "lat1:split_rows", "level0:fpn0x:tpc12"],
                 ["lateral:chain", "f1:dwsum+se16_proj"]),
     # lateral 3 of 2 x 2, SE maps of 4 pixels, every level odd, level 0 (17 x 17) not 4x lateral 1 (5 x 5)
     "34x34": (34, 34, 3, ("fp32", "split"),
@@ -98,9 +106,11 @@ CASES = {
     # features.1 148 columns wide: too many pixels for fir23's register tiles,
     # just inside fir's 64 KB of LDS (147 and 148 are the only such widths):
     # features.2 on fir, features.3 on exdw without SE; lateral 3 of 57 pixels
-    # with lateral 1 of 666: the big + reuse chain
+    # with lateral 1 of 666: the big + reuse chain; features.10 / 11 (3 x 19, not a
+    # seproj size) on the four-column exdw kernel without fc1 partials
     "72x592": (72, 592, 1, ("split",),
-               ["f2:fir:th*", "f3:exdw+project", "lateral_chain:split:big+reuse"], ["f2:fir23:t*", "f2:generic"]),
+               ["f2:fir:th*", "f3:exdw+project", "f3:exdw:rt:k3s1:cs16:xt4", "f10:exdw:rt:k5s1:cs32:xt4",
+                "f11:exdw:rt:k5s1:cs32:xt4", "lateral_chain:split:big+reuse"], ["f2:fir23:t*", "f2:generic"]),
     # features.1 176 columns wide: features.2 and features.3 (880 pixels) on the
     # generic three launches; level 0 (37 x 352) not 4x lateral 1 (10 x 88) with
     # a 66-pixel lateral 3: the fp32 big chain
