@@ -910,6 +910,90 @@ int kpd_detector_loss(const float* pooled, const float* box_w, const float* box_
                       float box_weight, float* loss, float* g_box_w, float* g_box_b, float* g_cls_w, float* g_cls_b,
                       void* stream);
 
+/* OKS pose tracking across frames on the device: greedy OKS
+ * association of every frame's poses with the live tracks of its sequence, and
+ * a One-Euro filter per joint along each track.  S independent sequences of B
+ * consecutive frames each, D pose slots per frame; the state is carried from
+ * call to call.
+ *   kpts   [S][B][D][K][2] fp32 (device);
+ *   scores [S][B][D] fp32 (device): a slot whose score is not > 0 (a NaN too)
+ *          is absent -- the rule of kpd_pose_nms, so a pose it suppressed is
+ *          absent here;
+ *   area   [S][B][D] in scaled units squared, kconf [S][B][D][K] per-keypoint
+ *          confidence or NULL, scale [S][B][2] = (sx, sy), multiplied onto
+ *          every x / y before differencing: all device;
+ *   sigmas [K]: a host array (it travels in the kernel arguments);
+ *   state  S x kpd_track_state_bytes of K bytes (device), 8-byte aligned,
+ *          opaque to the caller, updated in place.  All zero = no tracks, next
+ *          id 0, no frame seen.  One sequence's layout, T = KPD_TRACK_MAX_T
+ *          table entries: double filter[T][K][2][2] (per coordinate: x^, dx^ in
+ *          scaled units), float pose[T][K][2], float conf[T][K] (the last
+ *          matched raw pose), int32 filter_valid[T][K], int32 live[T], id[T],
+ *          age[T], hits[T], float area[T], sx[T], sy[T] (of the last matched
+ *          pose's frame), int32 next_id, int32 frames_seen, 8 bytes unused.
+ * Rules, per sequence, frames in order, all in double from the fp32 inputs.
+ *   1. OKS of live track t and present pose j: the pair formula of
+ *      kpd_pose_nms with the track's last matched RAW pose (its kpts, kconf,
+ *      area and that frame's scale) as pose i: den = (area_t + area_j) / 2 +
+ *      2^-52; keypoint k counts when kconf is NULL or both confidences are >
+ *      vis_threshold; dx = sx_t x_t - sx x_j, dy likewise; e_k = (dx^2 + dy^2) /
+ *      (2 sigma_k)^2 / den / 2; OKS = mean of exp(-e_k) over the counted k, 0
+ *      when none counts.
+ *   2. Greedy association: of the unmatched live tracks x unmatched present
+ *      poses whose OKS is > threshold the pair with the greatest OKS is
+ *      matched, ties to the lower track id, then the lower slot; repeated
+ *      until no such pair is left.  threshold and vis_threshold enter as the
+ *      fp32 values passed.
+ *   3. A matched track: its last pose becomes pose j, age 0, hits + 1;
+ *      track_id[j] = its id, track_hits[j] = hits, track_oks[j] = the OKS.
+ *   4. An unmatched live track: age + 1; freed when the age is then > max_age
+ *      (also in a frame without a present pose).
+ *   5. Unmatched present poses in slot order each take a free table entry
+ *      (those freed in step 4 of this frame count) as a new track: id = next
+ *      id, then incremented (ids are per sequence, start at 0 and are never
+ *      reused), hits 1, age 0, track_oks 0.  Without a free entry track_id =
+ *      -1, track_hits = 0.
+ *   6. An absent slot: track_id -1, track_hits 0, track_oks 0, kpts_out a copy.
+ *   7. counts [S][B][4] = (matched, born, dropped for lack of an entry, live
+ *      tracks after the frame).
+ * One-Euro smoothing (smooth != 0): per track, joint and coordinate in scaled
+ * units (x sx), double state.  For a matched or born track and a joint that
+ * counts in the current pose (kconf NULL or > vis_threshold): without valid
+ * filter state (a born track, or the joint did not count at the last match) x^
+ * = x, dx^ = 0; else te = (age before the match + 1) / fps, alpha(fc) = r / (r +
+ * 1) with r = 2 pi fc te, dx = (x - x^prev) / te, dx^ = alpha(d_cutoff) dx + (1 -
+ * alpha(d_cutoff)) dx^prev, fc = min_cutoff + beta |dx^|, x^ = alpha(fc) x + (1 -
+ * alpha(fc)) x^prev.  A joint that does not count passes through and
+ * invalidates its filter state.  kpts_out [S][B][D][K][2] fp32 = x^ / sx cast to
+ * fp32; a pose with track_id -1 passes through.  With smooth == 0 kpts_out may
+ * be NULL and is not written.  Matching always uses raw poses.
+ * Outputs (device): track_id, track_hits [S][B][D] int32, track_oks [S][B][D]
+ * double (may be NULL), kpts_out, counts.
+ * One launch, one 256-thread workgroup per sequence (a sequence's result does
+ * not depend on the others of the call), the frames in a loop inside it: the
+ * table's poses and the T x D OKS matrix in LDS, the association on one wave,
+ * no atomics.  Latency-bound by construction (a sequential dependency over
+ * frames on one CU per sequence).  Arguments are checked before any device
+ * work (KPD_EINVAL, the message names the argument): S, B >= 0, D in [0,
+ * KPD_TRACK_MAX_D], K in [1, KPD_TRACK_MAX_K], threshold in [0, 1), max_age >=
+ * 0, no NaN; with smooth min_cutoff, d_cutoff, fps > 0, beta >= 0, all finite.
+ * S = 0 or B = 0 returns KPD_OK without a launch; D = 0 is valid (frames still
+ * age tracks), and an array of zero elements may then be NULL.  The call does
+ * not synchronise.  Inputs of present poses are expected finite.  The defaults
+ * of dll.utils.PoseTracker are unmeasured and parity with any external tracker
+ * is not pinned.  tests/track_ref.py restates the rules in numpy.
+ * The state-size query returns the bytes of one sequence's state, 0 for K
+ * outside [1, KPD_TRACK_MAX_K]. */
+#define KPD_TRACK_MAX_T 64
+#define KPD_TRACK_MAX_D 64
+#define KPD_TRACK_MAX_K 32
+size_t kpd_track_state_bytes(int K);
+int kpd_track_poses(const float* kpts, const float* scores, const float* area, const float* kconf,
+                    const float* scale, const float* sigmas, int S, int B, int D, int K, float threshold,
+                    float vis_threshold, int max_age, int smooth, float min_cutoff, float beta, float d_cutoff,
+                    float fps, void* state, int32_t* track_id, int32_t* track_hits, double* track_oks,
+                    float* kpts_out, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,7 @@ EXPORTS = ("kpd_last_error", "kpd_version", "kpd_plan_create", "kpd_plan_set_ten
            "kpd_oks_match", "kpd_pose_nms", "kpd_flip_merge", "kpd_augment_batch", "kpd_bn_train_forward",
            "kpd_bn_train_backward", "kpd_roi_targets", "kpd_roi_features", "kpd_detector_features",
            "kpd_detector_targets", "kpd_detector_loss", "kpd_coord_loss", "kpd_softargmax_backward",
-           "kpd_roi_align_backward")
+           "kpd_roi_align_backward", "kpd_track_state_bytes", "kpd_track_poses")
 PRE_BATCH_CHUNK = 32   # KPD_PRE_BATCH_CHUNK: images per descriptor table (launches grow per chunk, not per image)
 # kpd_draw_poses (include/kpd.h): layer flags, images per descriptor table, one workgroup's tile, limits
 DRAW_BOXES, DRAW_LIMBS, DRAW_JOINTS, DRAW_HEAT = 1, 2, 4, 8
@@ -56,6 +56,10 @@ OKS_MAX_G = 64         # KPD_OKS_MAX_G: ground-truth slots per image
 POSE_NMS_MAX_D = 64    # KPD_POSE_NMS_MAX_D: pose slots per image, one lane each
 POSE_NMS_MAX_K = 32    # KPD_POSE_NMS_MAX_K: keypoints per pose
 POSE_NMS_HARD, POSE_NMS_SOFT, POSE_NMS_SOFT_LINEAR = 0, 1, 2
+# kpd_track_poses (include/kpd.h): limits of one call
+TRACK_MAX_T = 64       # KPD_TRACK_MAX_T: tracks per sequence, one lane each
+TRACK_MAX_D = 64       # KPD_TRACK_MAX_D: pose slots per frame
+TRACK_MAX_K = 32       # KPD_TRACK_MAX_K: keypoints per pose
 # kpd_flip_merge (include/kpd.h): limits of one call
 FLIP_MAX_K = 32        # KPD_FLIP_MAX_K: keypoints per pose
 FLIP_MAX_SIDE = 1024   # KPD_FLIP_MAX_SIDE: heatmap height / width
@@ -187,9 +191,13 @@ def load() -> ctypes.CDLL:
     lib.kpd_coord_loss.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_float, c_float] + [c_void_p] * 4
     lib.kpd_softargmax_backward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]
     lib.kpd_roi_align_backward.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] + [c_int] * 4 + [c_void_p] * 2
+    lib.kpd_track_state_bytes.argtypes = [c_int]
+    lib.kpd_track_poses.argtypes = [c_void_p] * 5 + [ctypes.POINTER(c_float)] + [c_int] * 4 + [c_float] * 2 + \
+        [c_int] * 2 + [c_float] * 4 + [c_void_p] * 7
     for name in EXPORTS:
         if name not in ("kpd_last_error", "kpd_version", "kpd_plan_destroy"):
             getattr(lib, name).restype = c_int
+    lib.kpd_track_state_bytes.restype = ctypes.c_size_t
     _lib = lib
     return lib
 

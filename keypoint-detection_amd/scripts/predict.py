@@ -36,6 +36,15 @@ Differences (documented in DESIGN.md):
   * ``--flip-test`` turns on the model's flip-test (a second forward over the
     mirrored image, the two heatmaps merged and decoded by kpd_flip_merge):
     overlays, label files and the printout come from the merged outputs.
+    Without the option nothing changes;
+  * ``--track`` (directory input only) treats the sorted files as consecutive
+    frames of one sequence: after the forwards (and pose-NMS) of every chunk
+    the poses go through ``dll.utils.PoseTracker`` (kpd_track_poses: greedy
+    OKS association with the live tracks, a One-Euro filter per joint along
+    each track; the state carries from chunk to chunk).  Overlays and label
+    files come from the smoothed poses, and ``<output>/tracks.txt`` lists every
+    present pose as ``frame id score cx cy w h`` + K groups ``x y v``.  The
+    tracker's defaults are unmeasured (no checkpoint, no sequence data).
     Without the option nothing changes.
 Runs on the HIP device (the accelerated path has no CPU fallback).
 """
@@ -54,7 +63,9 @@ from dll.configs import (BackboneConfig, KeypointHeadConfig, ModelConfig,  # noq
                          PersonDetectionConfig, TrainingConfig)
 from dll.data import ITransform  # noqa: E402
 from dll.models import MultiPersonKeypointModel  # noqa: E402
-from dll.utils import draw_poses, format_pose_labels, suppress_poses  # noqa: E402
+from dll.utils import PoseTracker, draw_poses, format_pose_labels, suppress_poses  # noqa: E402
+from dll.utils.draw import joint_classes, keypoints_tensor, person_boxes, visibilities_tensor  # noqa: E402
+from dll.utils.oks import keypoint_peaks, pose_scores  # noqa: E402
 
 KEYPOINT_NAMES = ["nose", "left_eye", "right_eye", "left_ear", "right_ear", "left_shoulder", "right_shoulder",
                   "left_elbow", "right_elbow", "left_wrist", "right_wrist", "left_hip", "right_hip", "left_knee",
@@ -114,6 +125,28 @@ def add_flip_test_argument(ap):
 
 def flip_test_enabled(args) -> bool:
     return args.flip_test == "on"
+
+
+def add_track_arguments(ap):
+    """--track [on|off] and its options: the bare option means on, the default is off."""
+    ap.add_argument("--track", nargs="?", const="on", default="off", choices=("on", "off"),
+                    help="directory input only: treat the sorted files as consecutive frames and track the poses "
+                         "across them (dll.utils.PoseTracker, kpd_track_poses); writes <output>/tracks.txt")
+    ap.add_argument("--track-threshold", type=float, default=0.3,
+                    help="OKS a pose needs with a track to continue it (unmeasured default)")
+    ap.add_argument("--track-max-age", type=int, default=10,
+                    help="frames a track survives without a match (unmeasured default)")
+    ap.add_argument("--track-fps", type=float, default=30.0, help="frame rate the One-Euro filter assumes")
+    ap.add_argument("--track-no-smooth", action="store_true",
+                    help="associate only: leave the keypoints as the forward decoded them")
+
+
+def track_options(args):
+    """``PoseTracker`` options of the parsed flags, None with --track off."""
+    if args.track == "off":
+        return None
+    return {"threshold": args.track_threshold, "max_age": args.track_max_age, "fps": args.track_fps,
+            "smooth": not args.track_no_smooth}
 
 
 def pose_nms_options(args):
@@ -242,6 +275,53 @@ def _slice_outputs(outputs, i, persons=None):
     return out
 
 
+def _frames_in_order(groups, n, device):
+    """The outputs of a chunk's forwards (``groups``: (image indices, batched
+    outputs) per forward) as one outputs dict of ``n`` frames in frame order,
+    zero padded to the chunk's largest person count: what ``PoseTracker.track``
+    and ``draw_poses`` read ('keypoints', 'visibilities', 'boxes' in slot
+    order, 'box_scores' = the base pose score, 0 for an absent or suppressed
+    slot, and 'keypoint_peaks' in place of the heatmaps, which are not copied)."""
+    shaped = []
+    for indices, out in groups:
+        kp = keypoints_tensor(out, len(indices))
+        P, K = kp.shape[1], kp.shape[2]
+        shaped.append((torch.tensor(indices, device=device), P, kp, visibilities_tensor(out, len(indices), P, K, device),
+                       person_boxes(out, len(indices), P, device), pose_scores(out, rescore=False),
+                       keypoint_peaks(out)))
+    P, K = max(g[1] for g in shaped), shaped[0][2].shape[2]
+    frames = {"keypoints": torch.zeros(n, P, 1, K, 2, device=device), "visibilities": torch.zeros(n, P, K, 3, device=device),
+              "boxes": torch.zeros(n, P, 4, device=device), "box_scores": torch.zeros(n, P, device=device),
+              "keypoint_peaks": torch.zeros(n, P, K, device=device)}
+    for idx, p, kp, vis, boxes, base, peaks in shaped:
+        frames["keypoints"][idx, :p, 0] = kp
+        frames["visibilities"][idx, :p] = vis
+        frames["boxes"][idx, :p] = boxes
+        frames["box_scores"][idx, :p] = base
+        frames["keypoint_peaks"][idx, :p] = peaks
+    return frames
+
+
+def format_track_lines(frame, outputs):
+    """One frame's lines of ``tracks.txt``: per present pose (track score > 0)
+    ``frame id score cx cy w h`` followed by K groups ``x y v`` -- floats as
+    %.6f, id -1 for a pose without a table entry, v the visibility class."""
+    kp = keypoints_tensor(outputs, 1).cpu()
+    P, K = kp.shape[1], kp.shape[2]
+    cls = joint_classes(visibilities_tensor(outputs, 1, P, K, "cpu")).clamp(min=0)
+    boxes = person_boxes(outputs, 1, P, "cpu")
+    ids, scores = outputs["track_ids"].cpu()[0], outputs["track_scores"].cpu()[0]
+    lines = []
+    for p in range(P):
+        if not float(scores[p]) > 0:
+            continue
+        vals = [str(int(frame)), str(int(ids[p])), f"{float(scores[p]):.6f}"] + [f"{float(v):.6f}" for v in boxes[0, p]]
+        for k in range(K):
+            vals += [f"{float(kp[0, p, k, 0]):.6f}", f"{float(kp[0, p, k, 1]):.6f}", str(int(cls[0, p, k]))]
+        lines.append(" ".join(vals) + "\n")
+    return "".join(lines)
+
+
 def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir=None, reference_zeros=False,
                       batch_size=64):
     """``predict_directory_nms`` without OKS pose-NMS: the reference's
@@ -251,7 +331,7 @@ def predict_directory(model, input_dir, transform, device, output_dir, *, gt_dir
 
 
 def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt_dir=None, reference_zeros=False,
-                          batch_size=64, pose_nms=None):
+                          batch_size=64, pose_nms=None, track=None):
     """Reference predict_directory (:133-160) as a batched device pipeline:
     the images with the reference's extensions, in sorted order, are decoded
     on the host; every chunk of at most ``batch_size`` is preprocessed by one
@@ -266,18 +346,28 @@ def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt
     through OKS pose-NMS at its images' own sizes first.  With an
     ``output_dir`` every forward's batched outputs are drawn onto its images by
     one ``draw_poses`` call and each image's overlay and label file are written
-    (``save_prediction``).  Returns
-    ``[(path, outputs_i)]`` with the shapes of a single-image call."""
+    (``save_prediction``).  With ``track`` (a ``PoseTracker`` of one sequence)
+    the files are consecutive frames: after its forwards and pose-NMS every
+    chunk's outputs are put back in frame order, padded to the chunk's largest
+    person count, and go through one ``track.track`` call (the state carries
+    from chunk to chunk; a file that failed to decode is not seen); drawing
+    and the label files use the tracked (smoothed) poses, the per-image
+    outputs carry ``track_ids``, and ``<output_dir>/tracks.txt`` lists every
+    present pose (``format_track_lines``; frame = the position in the sorted
+    file list).  Returns ``[(path, outputs_i)]`` with the shapes of a
+    single-image call."""
     from PIL import Image
     input_dir = Path(input_dir)
     if output_dir is not None:
         Path(output_dir).mkdir(parents=True, exist_ok=True)
     files = sorted(f for f in input_dir.glob("*") if f.suffix.lower() in IMAGE_EXTENSIONS)
     logging.info(f"Found {len(files)} images in {input_dir}")
-    results = []
+    if track is not None and reference_zeros:
+        raise ValueError("tracking needs poses: reference_zeros runs no forward")
+    results, track_lines = [], []
     for c0 in range(0, len(files), max(int(batch_size), 1)):
         decoded = []   # (path, image, boxes or None)
-        for path in files[c0:c0 + max(int(batch_size), 1)]:
+        for frame, path in enumerate(files[c0:c0 + max(int(batch_size), 1)], c0):
             try:
                 image = Image.open(path).convert("RGB")
                 gt = Path(gt_dir) / f"{path.stem}.txt" if gt_dir else None
@@ -287,16 +377,18 @@ def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt
             except Exception as e:
                 logging.error(f"Error processing {path.name}: {e}")
                 continue
-            decoded.append((path, image, boxes))
+            decoded.append((path, image, boxes, frame))
         if not decoded:
             continue
         x = transform.batch([d[1] for d in decoded]).to(device)
         given = [i for i, d in enumerate(decoded) if d[2] is not None]
         other = [i for i, d in enumerate(decoded) if d[2] is None]
-        per_image, drawn = {}, {}
+        per_image, drawn, groups = {}, {}, []
 
         def draw(indices, out):   # one draw call per forward, on its batched outputs, at the original resolutions
-            if output_dir is not None:
+            if track is not None:
+                groups.append((indices, out))   # drawn after the tracker, from the smoothed poses
+            elif output_dir is not None:
                 drawn.update(zip(indices, draw_poses([decoded[i][1] for i in indices], out)))
 
         with torch.no_grad():
@@ -320,7 +412,16 @@ def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt
                 draw(other, out)
                 for j, i in enumerate(other):
                     per_image[i] = (mode, _slice_outputs(out, j))
-        for i, (path, _, _) in enumerate(decoded):
+            if track is not None:
+                tracked = track.track(_frames_in_order(groups, len(decoded), device), [d[1].size for d in decoded])
+                if output_dir is not None:
+                    drawn.update(enumerate(draw_poses([d[1] for d in decoded], tracked)))
+                for i, (mode, outputs) in per_image.items():
+                    p = outputs["keypoints"].shape[1]
+                    for k in ("track_ids", "track_hits", "track_scores", "keypoints", "keypoints_raw"):
+                        if k in tracked:
+                            outputs[k] = tracked[k][i:i + 1, :p]
+        for i, (path, _, _, frame) in enumerate(decoded):
             mode, outputs = per_image[i]
             logging.info(f"{path.name}: boxes from {mode}")
             if mode == "person detector":
@@ -332,7 +433,11 @@ def predict_directory_nms(model, input_dir, transform, device, output_dir, *, gt
                 output_path = output_path_for(output_dir, path)
                 save_prediction(drawn[i], outputs, output_path)
                 logging.info(f"Saved visualization to {output_path}")
+            if track is not None and output_dir is not None:
+                track_lines.append(format_track_lines(frame, outputs))
             results.append((path, outputs))
+    if track is not None and output_dir is not None:
+        (Path(output_dir) / "tracks.txt").write_text("".join(track_lines))
     return results
 
 
@@ -352,7 +457,12 @@ def main(argv=None):
     ap.add_argument("--size", default=None, help="HxW input size (default: input_size square)")
     add_pose_nms_arguments(ap)
     add_flip_test_argument(ap)
+    add_track_arguments(ap)
     args = ap.parse_args(argv)
+    if track_options(args) is not None and Path(args.input).is_file():
+        ap.error("--track needs a directory --input: the sorted files are the frames of the sequence")
+    if track_options(args) is not None and args.reference_zeros:
+        ap.error("--track needs poses: --reference-zeros runs no forward")
     setup_logging()
     cfg = load_config(args.config)
     device = torch.device(args.device)
@@ -376,8 +486,13 @@ def main(argv=None):
                                                   return_outputs=True, pose_nms=pose_nms_options(args))[1]))
         logging.info(f"Saved visualization to {output_path}")
     else:
+        tracker = None
+        if track_options(args) is not None:
+            tracker = PoseTracker(cfg["model"]["keypoint_head"]["num_keypoints"], device=device, **track_options(args))
+            logging.info("tracking on: the sorted files are consecutive frames of one sequence")
         results = predict_directory_nms(model, inp, transform, device, args.output, gt_dir=gt,
-                                        reference_zeros=args.reference_zeros, pose_nms=pose_nms_options(args))
+                                        reference_zeros=args.reference_zeros, pose_nms=pose_nms_options(args),
+                                        track=tracker)
     logging.info("Prediction completed successfully!")
     return {"model": model, "results": results}
 
