@@ -872,8 +872,14 @@ int kpd_detector_features(kpd_plan* plan, const float* image, int B, int C, int 
  * over the present GTs, arg = its slot (ties: the lower slot); best >= pos_thr:
  * assign[n] = arg; neg_thr <= best < pos_thr: -2 (ignored); otherwise -1
  * (negative).  Then, for each present GT g with gmax_g = max_n IoU(n, g) > 0,
- * every anchor with IoU(n, g) >= gmax_g - tie_eps gets assign[n] = its own arg
- * (low-quality matches; overrides -1 / -2).  n_pos[b] = the number of
+ * every anchor with IoU(n, g) >= gmax_g - min(tie_eps, gmax_g / 2) gets
+ * assign[n] = its own arg (low-quality matches; overrides -1 / -2).  The band
+ * is capped at half the maximum so that a sub-pixel GT, whose gmax is below
+ * tie_eps, claims the anchors that tie its maximum and not every anchor of the
+ * image; for gmax_g >= 2 tie_eps the band is tie_eps.  An anchor whose IoU
+ * with every present GT is 0 is never positive.  A present row whose IoU is 0
+ * everywhere (an infinite width or centre, a box outside the image) has gmax 0
+ * and matches nothing.  n_pos[b] = the number of
  * assign >= 0; an image without a present GT is all -1.  assign [B][A] int32,
  * n_pos [B] int32, gt_best [B][G] (gmax; 0 for an absent row; nullable).
  * gt_boxes may be NULL when G = 0.  Two launches: the per-GT maxima by
@@ -893,7 +899,12 @@ int kpd_detector_targets(const float* anchors, const float* gt_boxes, int B, int
  * log(1-p) (t = 0), the logs through a stable softplus; ignored anchors
  * contribute 0.  Box term on positives: smooth-L1 (beta) of d - target, target
  * = ((gcx-ax)/aw, (gcy-ay)/ah, log(gw/aw), log(gh/ah)), the decode's inverse
- * without its exp clip.  N = max(1, sum_b n_pos[b]), read on the device.
+ * without its exp clip.  N = max(1, sum_b n_pos[b]), read on the device: it
+ * follows n_pos alone, not the number of non-negative entries of assign.
+ * assign need not come from the matching: an entry >= G (G = 0 included) is
+ * treated as -2 and an entry below -2 as -1, bit for bit; an entry in [0, G)
+ * must name a present row of gt_boxes (the row is read as given: an absent
+ * row's zeros or NaN go into the log targets).
  *   loss[0] = (sum FL + box_weight * sum SL1) / N, loss[1] = sum FL / N,
  *   loss[2] = sum SL1 / N
  * and g_* = d loss[0] / d parameter in closed form, each of the parameter's
@@ -901,7 +912,7 @@ int kpd_detector_targets(const float* anchors, const float* gt_boxes, int B, int
  * loss alone (the same loss bits).  One fused pass over pooled (no head map or
  * gradient map goes through memory) with per-workgroup partials, fp32 within a
  * block of 56 cells and across the blocks a workgroup owns (a map that depends
- * on B alone), and one launch that sums the partials in index order in
+ * on B alone; the bias gradients' column sums in double), and one launch that sums the partials in index order in
  * double: no floating-point atomics, two calls are bit-identical.  alpha in
  * [0, 1], gamma >= 0, beta > 0, box_weight >= 0. */
 int kpd_detector_loss(const float* pooled, const float* box_w, const float* box_b, const float* cls_w,

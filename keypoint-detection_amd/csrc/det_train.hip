@@ -8,8 +8,8 @@
 //                          (atomicMax on the bits of the non-negative fp32 IoU:
 //                          order-independent, so deterministic);
 //     det_assign_kernel    per-anchor assignment (best GT, ignore band,
-//                          low-quality matches within tie_eps of a GT's
-//                          maximum) and the per-image positive count.
+//                          low-quality matches within min(tie_eps, gmax / 2) of
+//                          a GT's maximum) and the per-image positive count.
 //   kpd_detector_loss      focal + smooth-L1 loss and the closed-form gradients
 //                          of box_heads[0] / cls_heads[0], two launches:
 //     det_loss_kernel      one pass over the pooled features [B][3136][128].
@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256) void det_assign_kernel(const float* __restrict
     if (!(v > 0.f)) v = 0.f;
     if (v > best) { best = v; arg = g; }   // ties: the lower slot
     const float gm = sgmax[g];
-    if (gm > 0.f && v >= gm - tie_eps) low = true;
+    // the band is capped at half the maximum: a sub-pixel GT (gmax < tie_eps) claims its tie set, not every anchor
+    if (gm > 0.f && v >= gm - fminf(tie_eps, gm / 2.f)) low = true;
   }
   int a = -1;
   if (arg >= 0) {
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(512) void det_loss_kernel(
   for (int it = tid; it < (kRows - G56) * kPP; it += 512) pool[G56 * kPP + it] = 0.f;
   for (int it = tid; it < kRows * kHS; it += 512) hg[it] = 0.f;
   f32x4 wacc[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  float bacc = 0.f;
+  double bacc = 0.0;           // (threads 0..44) dL/db of one head column over the workgroup's row blocks
   double lc = 0.0, lb = 0.0;   // (thread 0) the workgroup's class and box sums
   // row of the 48 x 128 head matrix: box_heads[0] ++ cls_heads[0], rows 45..47 zero
   auto wrow = [&](int col) -> const float* {
@@ -218,7 +219,8 @@ __global__ __launch_bounds__(512) void det_loss_kernel(
       const int anc = (i * G56 + j) * NA + a;
       float* h = hg + j * kHS;
       int asg = assign[(size_t)b * A + anc];
-      if (asg >= G) asg = -2;   // (never from kpd_detector_targets; keeps the GT read in bounds)
+      // (never from kpd_detector_targets; keeps the GT read in bounds.  kpd.h: >= G acts as -2, < -2 as -1)
+      if (asg >= G) asg = -2;
       const float z = h[36 + a];
       float gz = 0.f;
       if (asg != -2) {
@@ -267,10 +269,15 @@ __global__ __launch_bounds__(512) void det_loss_kernel(
     }
     if (want_grad) {
       // 4. dL/db: column sums over the row's cells; dL/dW += gy^T x, wave w owning input channels 16w .. 16w+15
+      //    (the column sums in double: with near-constant logits, as after the bias initialisation, the 56 addends
+      //    are almost equal and an fp32 running sum rounds the same way in every block -- 7e-7 of dL/db, §3j)
       if (tid < kHC) {
-        float s = 0.f;
-        for (int j = 0; j < G56; ++j) s += hg[j * kHS + tid];
-        bacc += s;
+        double s0 = 0.0, s1 = 0.0;
+        for (int j = 0; j < G56; j += 2) {
+          s0 += (double)hg[j * kHS + tid];
+          s1 += (double)hg[(j + 1) * kHS + tid];
+        }
+        bacc += s0 + s1;
       }
 #pragma unroll
       for (int kk = 0; kk < kRows / 4; ++kk) {
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(512) void det_loss_kernel(
     for (int mb = 0; mb < 3; ++mb)
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[(mb * 16 + g * 4 + e) * kC + wave * 16 + r16] = wacc[mb][e];
-    if (tid < 48) o[48 * kC + tid] = tid < kHC ? bacc : 0.f;
+    if (tid < 48) o[48 * kC + tid] = tid < kHC ? (float)bacc : 0.f;
   }
 }
 

@@ -24,7 +24,8 @@ class DetectionLoss(nn.Module):
     Matching: an anchor whose best IoU over the labelled boxes is at least
     ``pos_thr`` is positive for that box, in [``neg_thr``, ``pos_thr``) ignored,
     below negative; every labelled box also claims the anchors within
-    ``tie_eps`` of its own best IoU.  Class term: focal loss (``alpha``,
+    min(``tie_eps``, half its own best IoU) of that best IoU, so a sub-pixel
+    box keeps to the anchors that tie for it.  Class term: focal loss (``alpha``,
     ``gamma``) of the sigmoid logits; box term: smooth-L1 (``beta``) of the raw
     deltas against the decode's inverse, weighted by ``box_weight``."""
 

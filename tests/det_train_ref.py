@@ -53,7 +53,9 @@ def match(anchors, gt_boxes, B, H, W, pos_thr=0.5, neg_thr=0.4, tie_eps=1e-5, dt
     for b in range(B):
         g32 = gt_boxes[b].to(torch.float32)
         pres = present(g32)
-        gb = torch.nan_to_num(g32, nan=0.0).to(dtype)
+        # NaN -> 0 (the row is absent anyway); an infinity stays one, as the device sees it (torch.nan_to_num
+        # would make it the largest finite number, and the box's IoU a positive denormal instead of 0)
+        gb = torch.where(torch.isnan(g32), torch.zeros_like(g32), g32).to(dtype)
         iou = box_iou_cxcywh(an, gb)                       # [A, G]
         iou = torch.where(iou > 0, iou, torch.zeros_like(iou))
         ious.append(iou)
@@ -68,7 +70,9 @@ def match(anchors, gt_boxes, B, H, W, pos_thr=0.5, neg_thr=0.4, tie_eps=1e-5, dt
         a = torch.where(best >= pt, arg, a)
         gmax = torch.where(pres, iou.max(dim=0).values, torch.zeros(G, dtype=dtype))
         gt_best[b] = gmax
-        low = (pres[None, :] & (gmax[None, :] > 0) & (iou >= gmax[None, :] - te)).any(dim=1)
+        # the band is capped at half the maximum, so a sub-pixel GT (gmax < tie_eps) keeps to its tie set
+        band = torch.minimum(te, gmax / 2)
+        low = (pres[None, :] & (gmax[None, :] > 0) & (iou >= gmax[None, :] - band[None, :])).any(dim=1)
         a = torch.where(low, arg, a)
         assign[b] = a.to(torch.int32)
     return dict(assign=assign, n_pos=(assign >= 0).sum(dim=1).to(torch.int32), gt_best=gt_best, iou=ious)
@@ -76,8 +80,8 @@ def match(anchors, gt_boxes, B, H, W, pos_thr=0.5, neg_thr=0.4, tie_eps=1e-5, dt
 
 def threshold_margin(m, pos_thr=0.5, neg_thr=0.4, tie_eps=1e-5):
     """(thr, tie) of a float64 ``match`` result: the smallest distance of any anchor's best IoU to pos_thr /
-    neg_thr, and of any IoU to its GT's gmax - tie_eps (at most tie_eps: the maximum itself); inf without a
-    present GT."""
+    neg_thr, and of any IoU to its GT's gmax - min(tie_eps, gmax / 2) (at most that band: the maximum itself);
+    inf without a present GT."""
     thr = tie = math.inf
     for b, iou in enumerate(m["iou"]):
         if iou is None:
@@ -88,7 +92,8 @@ def threshold_margin(m, pos_thr=0.5, neg_thr=0.4, tie_eps=1e-5):
             continue
         best = iou[:, on].max(dim=1).values
         thr = min(thr, float((best - pos_thr).abs().min()), float((best - neg_thr).abs().min()))
-        tie = min(tie, float((iou[:, on] - (gm[on][None, :] - tie_eps)).abs().min()))
+        band = torch.clamp(gm[on] / 2, max=tie_eps)
+        tie = min(tie, float((iou[:, on] - (gm[on] - band)[None, :]).abs().min()))
     return thr, tie
 
 
@@ -117,15 +122,16 @@ def box_targets(anchors, gt_boxes, assign, H, W, dtype):
 
 
 def loss_and_grads(x, box_w, box_b, cls_w, cls_b, anchors, gt_boxes, assign, H, W, alpha=0.25, gamma=2.0,
-                   beta=1.0 / 9, box_weight=1.0):
+                   beta=1.0 / 9, box_weight=1.0, n=None):
     """Closed forms in float64 -> dict(loss, cls, box (python floats), n (N), g_box_w [36,128], g_box_b [36],
-    g_cls_w [9,128], g_cls_b [9]).  loss = (sum FL + box_weight sum SL1) / N, cls = sum FL / N, box = sum SL1 / N."""
+    g_cls_w [9,128], g_cls_b [9]).  loss = (sum FL + box_weight sum SL1) / N, cls = sum FL / N, box = sum SL1 / N.
+    N = max(1, n), n = the number of assign >= 0 unless given (the device reads it from n_pos)."""
     dt = torch.float64
     x = x.to(dt)
     B = x.shape[0]
     d, z = heads(x, box_w.to(dt), box_b.to(dt), cls_w.to(dt), cls_b.to(dt))
     pos, ign = assign >= 0, assign == -2
-    N = max(1, int(pos.sum()))
+    N = max(1, int(pos.sum()) if n is None else int(n))
     p = torch.sigmoid(z)
     q = torch.sigmoid(-z)
     logp, logq = -F.softplus(-z), -F.softplus(z)
@@ -153,13 +159,14 @@ def loss_and_grads(x, box_w, box_b, cls_w, cls_b, anchors, gt_boxes, assign, H, 
 
 
 def chain(x, box_w, box_b, cls_w, cls_b, anchors, gt_boxes, assign, H, W, alpha=0.25, gamma=2.0, beta=1.0 / 9,
-          box_weight=1.0, dtype=torch.float64):
+          box_weight=1.0, dtype=torch.float64, n=None):
     """The same loss as differentiable torch ops in ``dtype`` -> (loss, cls part, box part), 0-d tensors; the
-    parameters are used as given (leaf tensors of ``dtype`` that require grad get their gradients by autograd)."""
+    parameters are used as given (leaf tensors of ``dtype`` that require grad get their gradients by autograd).
+    ``n`` as in loss_and_grads."""
     x = x.to(dtype)
     d, z = heads(x, box_w, box_b, cls_w, cls_b)
     pos, ign = assign >= 0, assign == -2
-    N = max(1, int(pos.sum()))
+    N = max(1, int(pos.sum()) if n is None else int(n))
     p, q = torch.sigmoid(z), torch.sigmoid(-z)
     fl1 = alpha * q ** gamma * F.softplus(-z)
     fl0 = (1 - alpha) * p ** gamma * F.softplus(z)
